@@ -21,7 +21,11 @@ are timed on the gradient buffer at start-up and the faster one is used (--grad-
 xgmi / rccl forces one; the JSON config records the timings and the choice).  Nothing is skipped inside the timed
 region.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [...]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [...]
+
+A plain run sets up, warms up, times exactly --steps steps and prints one JSON line
+(`ms_per_step` = milliseconds per timed step).  `--dump-outputs DIR` also writes the last timed
+step's results as .npy files; `--full` is where anything beyond the headline figure belongs.
 
 `--gpus N` without torchrun starts N ranks on this node itself (parallel/launch.py); under
 torchrun it must equal WORLD_SIZE.
@@ -88,7 +92,32 @@ def parse_args(argv=None):
     p.add_argument("--shared-gpu", action="store_true",
                    help="rehearsal: every rank on cuda:0 with a gloo process group (xGMI all-reduce only; "
                         "checks the multi-rank step on a one-GPU box)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step left with the caller of the training "
+                        "path (loss, flat fp32 parameters, optimizer slots) as DIR/<name>.npy (float32); the same "
+                        "arguments give the same inputs, so two builds can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure (extra measurements, comparisons, per-kernel numbers); "
+                        "a plain run sets up, warms up, times --steps steps and prints the result line. The headline "
+                        "run has no such extras today, so --full runs the same steps")
     return p.parse_args(argv)
+
+
+def dump_outputs(tr, path):
+    """What a caller of SageTrainer.step() holds after the last timed step: the step's loss, the
+    flat fp32 parameters (trainer layout, logical_params() unpacks them) and the optimizer's two
+    slots.  The fused single-process optimizer launch consumes the split-K gradient partials
+    without storing the reduced gradient, so there is no gradient array to write."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    cap = 4 * 1024 * 1024  # elements per array: 16 MB each, under 64 MB in all
+    for name, t in (("loss", tr.loss), ("params", tr.flat), ("adam_m", tr.m), ("adam_v", tr.v)):
+        a = t.detach().to(torch.float32).cpu().numpy().reshape(-1)
+        if a.size > cap:  # a fixed sample of a larger array (the same elements in every run)
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _cpu_baseline():
@@ -268,6 +297,8 @@ def main(argv=None):
     ms = elapsed * 1000.0 / max(args.steps, 1)
     value = world * B * args.steps / elapsed
     base_value, base_note = _cpu_baseline()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(tr, args.dump_outputs)
     if rank == 0:
         log(f"loss after warmup {first_loss:.4f} -> after timed steps {last_loss:.4f}")
         out = {

@@ -42,6 +42,36 @@ def test_bench_single_gpu_json():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_repeatable(tmp_path):
+    # --dump-outputs writes what the last timed step left (loss, flat parameters, Adam slots) as
+    # float32 .npy files.  The same arguments give the same graph, features, weights and sample
+    # stream, and every reduction of the step runs in a fixed order (split-K slabs summed in slab
+    # order, no floating-point atomics), so two runs agree bit for bit.  --steps is the number of
+    # timed steps (7 here: one remainder graph, no multiple of the captured 32) and --full is
+    # accepted and changes nothing about them.
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = _run([sys.executable, "bench.py", "--gpus", "1", "--num-nodes", "200000", "--steps", "7", "--warmup", "3",
+                    "--dump-outputs", str(d)] + extra)
+        assert out["steps"] == 7 and out["warmup"] == 3 and out["ms_per_step"] > 0
+        # samples/s x s/step = batch (ms_per_step is rounded to 4 places: 0.1 % at 0.07 ms)
+        assert abs(out["value"] * out["ms_per_step"] / 1e3 - 1024) < 0.002 * 1024
+        arrs = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert set(arrs) == {"loss", "params", "adam_m", "adam_v"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        assert arrs["loss"].shape == (1,) and arrs["params"].shape == arrs["adam_m"].shape == arrs["adam_v"].shape
+        assert abs(float(arrs["loss"][0]) - out["config"]["loss_first_last"][1]) <= 1e-4  # rounded to 4 places
+        assert np.abs(arrs["adam_m"]).max() > 0 and arrs["adam_v"].min() >= 0
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--no-graph"], ["--grad-reduce-dtype", "bf16"], ["--grad-buckets", "2"]],
                          ids=["captured", "eager", "bf16_allreduce", "two_buckets"])
 def test_bench_distributed_path_one_rank(extra):
