@@ -186,6 +186,16 @@ hipError_t eh_flow_block(const int64_t* src, const int64_t* offs, const int64_t*
                          int64_t* edge_index, int64_t* perm, int64_t* indptr, int64_t* counts, int64_t* last_new,
                          int64_t* cnt_new, int32_t* overflow, hipStream_t s);
 
+// node_embed.hip (node rows -> embedding bags over the HBM sparse-feature CSR / id column)
+// mode 0 bag_sum, 1 bag_mean, 2 id; num_rows < 0 in id mode without node_ids: ids = rows
+hipError_t eh_node_bag_fwd(const int64_t* rows, int64_t n, const int64_t* indptr, const int64_t* values, int64_t nnz,
+                           const int64_t* node_ids, int64_t num_rows, const float* table, int64_t V, int D, float* out,
+                           int64_t ld, int64_t col, int mode, int hash, hipStream_t s);
+// dtable [V, D] is added to (the caller zeroes it)
+hipError_t eh_node_bag_bwd(const int64_t* rows, int64_t n, const int64_t* indptr, const int64_t* values, int64_t nnz,
+                           const int64_t* node_ids, int64_t num_rows, const float* dout, int64_t ld, int64_t col,
+                           int64_t V, int D, float* dtable, int mode, int hash, hipStream_t s);
+
 // optim.hip
 hipError_t eh_flat_optim(float* p, const float* g, float* m, float* v, int64_t n, int64_t* step, float lr, float b1,
                          float b2, float eps, float wd, float grad_scale, int kind, hipStream_t s);

@@ -10,7 +10,7 @@ import shutil
 import numpy as np
 
 __all__ = ["DataSet", "get_dataset", "dataset_names", "Cora", "Citeseer", "Pubmed", "PPI", "Reddit", "FB15K",
-           "FB15K237", "WN18", "Mutag", "MovieLens1M", "TestData", "Community"]
+           "FB15K237", "WN18", "Mutag", "MovieLens1M", "TestData", "Community", "CoraSparse"]
 
 _HOME = os.environ.get("EULER_AMD_DATA", os.path.join(os.path.expanduser("~"), ".euler_amd", "data"))
 
@@ -145,6 +145,11 @@ class _Citation(DataSet):
     def _split_start(self, n):
         return int(round(self.test_start_num * n / max(self.num_nodes, 1)))
 
+    def _extra_features(self, i, words):
+        """further features of synthetic node ``i`` (``words``: its drawn word ids); draws
+        nothing, so a subclass's extras leave the generated graph as it is"""
+        return []
+
     def synthesize(self, rng):
         n, F, L = self.total_size, self.feature_dim, self.label_dim
         cls = rng.integers(0, max(L, 1), n)
@@ -166,7 +171,8 @@ class _Citation(DataSet):
                 lab = np.eye(L)[cls[i]]
             t = "train" if i < start else "test"
             nodes.append(_node(i, t, [{"name": "label", "type": "dense", "value": lab.tolist()},
-                                      {"name": "feature", "type": "dense", "value": feat.tolist()}]))
+                                      {"name": "feature", "type": "dense", "value": feat.tolist()}] +
+                               self._extra_features(i, words)))
         m = int(n * self.avg_degree / 2)
         src = rng.integers(0, n, m)
         same = rng.random(m) < 0.8
@@ -230,6 +236,26 @@ class Cora(_Citation):
 
     def convert2json(self, d):
         return _planetoid_like(self, os.path.join(d, "cora.content"), os.path.join(d, "cora.cites"))
+
+
+class CoraSparse(Cora):
+    """Cora's synthetic generator plus a sparse feature ``words``: the node's distinct word
+    ids (the bag its dense ``feature`` row counts).  Every 16th node has no ``words`` entry,
+    so lookups meet the default id.  For the sparse-feature / id-embedding encoder inputs
+    (``ShallowEncoder``: reference tf_euler/python/utils/encoders.py:32-171)."""
+
+    name = "cora_sparse"
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.origin_files = []  # always synthetic: the raw Cora files carry no id lists
+        self.sparse_fea_idx = "words"
+        self.sparse_fea_max_id = self.feature_dim - 1
+
+    def _extra_features(self, i, words):
+        if i % 16 == 15:
+            return []
+        return [{"name": "words", "type": "sparse", "value": [int(w) for w in np.unique(words)]}]
 
 
 class Citeseer(_Citation):
@@ -685,7 +711,7 @@ class TestData(DataSet):
 _REGISTRY = {
     "cora": Cora, "citeseer": Citeseer, "pubmed": Pubmed, "ppi": PPI, "reddit": Reddit, "fb15k": FB15K,
     "fb15k-237": FB15K237, "wn18": WN18, "mutag": Mutag, "movielens-1m": MovieLens1M, "test_data": TestData,
-    "community": Community,
+    "community": Community, "cora_sparse": CoraSparse,
 }
 
 

@@ -60,8 +60,10 @@ class Ctx:
     def feature_dtype(self):
         return torch.float32 if self.params.get("device_feature_dtype", "bf16") == "fp32" else torch.bfloat16
 
-    def upload(self, default_node_type=-1, features=(), feature_dims=(), label=None, label_dim=None, node_type=None):
-        """the engine's graph (structure + the named dense feature / label columns) in HBM;
+    def upload(self, default_node_type=-1, features=(), feature_dims=(), label=None, label_dim=None, node_type=None,
+               sparse_features=()):
+        """the engine's graph (structure + the named dense feature / label columns and the
+        named sparse feature columns, ``DeviceGraph.sparse``) in HBM;
         ``params["device_graph_factory"](rank, device)`` supplies it instead (e.g. a
         ``DeviceGraph.synthetic`` 100M-node graph generated straight in HBM, no engine)"""
         from euler_amd.graph.device_graph import DeviceGraph
@@ -75,6 +77,8 @@ class Ctx:
         kw = {}
         if label is not None:
             kw.update(label=label, label_dim=label_dim)
+        if sparse_features not in (None, -1, ()) and len(sparse_features):
+            kw.update(sparse_features=list(sparse_features))
         nt = self.node_type(default_node_type) if node_type is None else node_type
         # every rank uploads together: with 2+ ranks on a node the export happens once
         # (local rank 0 into /dev/shm, the others map it: graph/device_graph.py shared_export)
@@ -320,6 +324,14 @@ def row_sparse(c: Ctx, rows: int, sharded: bool = False) -> bool:
     return bool(sharded) or int(rows) >= ROW_SPARSE_AUTO_ROWS
 
 
+def _node_encoder_upload(c: Ctx, ne, **kw):
+    """the graph with a ShallowEncoder's inputs in HBM: its dense feature columns and its
+    sparse feature columns (models/node_inputs.py reads them; the id embedding needs none)"""
+    return c.upload(features=ne.feature_idx if ne.use_feature else (),
+                    feature_dims=ne.feature_dim if ne.use_feature else (),
+                    sparse_features=ne.sparse_feature_idx if ne.use_sparse_feature else (), **kw)
+
+
 # ----------------------------------------------------------------------------------- builders
 @register("knowledge_graph", _is_kg)
 def _kg(c: Ctx):
@@ -417,8 +429,7 @@ def _dgi(c: Ctx):
     from euler_amd.models.dgi_trainer import DgiTrainer
 
     ne = c.model._target_encoder._node_encoder
-    g = c.upload(c.model.node_type, features=ne.feature_idx if ne.use_feature else (),
-                 feature_dims=ne.feature_dim if ne.use_feature else ())
+    g = _node_encoder_upload(c, ne, default_node_type=c.model.node_type)
     return DgiTrainer(c.model, g, c.batch, **c.opt_kw())
 
 
@@ -438,9 +449,13 @@ def _usol(c: Ctx):
     from euler_amd.models.encoder_trainer import UnsupSolutionTrainer
 
     ne = getattr(c.model.target_encoder, "_node_encoder", None)
-    if ne is None or not getattr(ne, "use_feature", False):
-        raise ValueError("device_graph=True trains UnsuperviseSolution over dense-feature SageEncoders")
-    g = c.upload(features=ne.feature_idx, feature_dims=ne.feature_dim)
+    ne_c = getattr(c.model.context_encoder, "_node_encoder", None)
+    if ne is None or ne_c is None:
+        raise ValueError("device_graph=True trains UnsuperviseSolution over SageEncoders")
+    sparse = [] if not ne.use_sparse_feature else list(ne.sparse_feature_idx)
+    sparse += [n for n in (ne_c.sparse_feature_idx if ne_c.use_sparse_feature else []) if n not in sparse]
+    g = c.upload(features=ne.feature_idx if ne.use_feature else (),
+                 feature_dims=ne.feature_dim if ne.use_feature else (), sparse_features=sparse)
     return UnsupSolutionTrainer(c.model, g, c.batch, **c.opt_kw())
 
 
@@ -452,10 +467,9 @@ def _sol(c: Ctx):
 
     ne = getattr(c.model.encoder, "_node_encoder", None)
     lab = c.model.get_label_fn
-    if ne is None or not getattr(ne, "use_feature", False) or not hasattr(lab, "label_idx"):
-        raise ValueError("device_graph=True trains SuperviseSolution over a dense-feature SageEncoder "
-                         "with GetLabelFromFea labels")
-    g = c.upload(features=ne.feature_idx, feature_dims=ne.feature_dim, label=lab.label_idx, label_dim=lab.label_dim)
+    if ne is None or not hasattr(lab, "label_idx"):
+        raise ValueError("device_graph=True trains SuperviseSolution over a SageEncoder with GetLabelFromFea labels")
+    g = _node_encoder_upload(c, ne, label=lab.label_idx, label_dim=lab.label_dim)
     return SolutionTrainer.from_model(c.model, g, c.batch, **c.opt_kw())
 
 
@@ -501,9 +515,8 @@ def _enc(c: Ctx):
     # the device, the model's own encode (models/encoder_trainer.py)
     from euler_amd.models.encoder_trainer import EncoderFlowTrainer
 
-    ne = c.model._encoder._node_encoder
-    g = c.upload(features=ne.feature_idx if ne.use_feature else (), feature_dims=ne.feature_dim if ne.use_feature
-                 else (), label=c.model.label_idx, label_dim=c.model.label_dim)
+    g = _node_encoder_upload(c, c.model._encoder._node_encoder, label=c.model.label_idx,
+                             label_dim=c.model.label_dim)
     return EncoderFlowTrainer.from_model(c.model, g, c.batch, **c.opt_kw())
 
 

@@ -44,6 +44,39 @@ def _export_local(eng, names, dims, label, label_dim):
     return out
 
 
+_SPARSE_CHUNK = 1 << 16  # node ids per sparse-feature query
+
+
+def _export_sparse(ids, names):
+    """the sparse feature columns ``names`` of the nodes ``ids`` (engine row order) as host
+    CSR arrays ``sp<k>_indptr`` int64 [N + 1] / ``sp<k>_values`` int64 [nnz] (the engine's
+    uint64 ids reinterpreted, as ``SparseEmbedding.forward`` reads them); rows without the
+    feature stay empty.  Fetched with the generic ragged feature query in bounded chunks of
+    ids, so local, ``local_sharded`` and remote engines take one code path."""
+    from euler_amd.ops import graph_api as G
+
+    ids = np.asarray(ids, dtype=np.uint64).reshape(-1)
+    lens = [[] for _ in names]
+    vals = [[] for _ in names]
+    for s in range(0, len(ids), _SPARSE_CHUNK):
+        res = G._feature_query("v", "nodes", np.ascontiguousarray(ids[s: s + _SPARSE_CHUNK]), "sparse_", list(names))
+        for k, (idx, v) in enumerate(res):
+            idx = np.asarray(idx).reshape(-1, 2).astype(np.int64)
+            v = np.asarray(v)
+            v = (v if v.dtype == np.uint64 else v.astype(np.uint64)).view(np.int64)
+            b, ln = idx[:, 0], np.maximum(idx[:, 1] - idx[:, 0], 0)
+            # the ragged rows in order (a plain slice when they tile the value array)
+            take = np.repeat(b - (np.cumsum(ln) - ln), ln) + np.arange(int(ln.sum()))
+            lens[k].append(ln)
+            vals[k].append(v[take])
+    out = {}
+    for k in range(len(names)):
+        ln = np.concatenate(lens[k]) if lens[k] else np.zeros(0, np.int64)
+        out["sp%d_indptr" % k] = np.concatenate([[0], np.cumsum(ln)]).astype(np.int64)
+        out["sp%d_values" % k] = np.concatenate(vals[k]).astype(np.int64) if vals[k] else np.zeros(0, np.int64)
+    return out
+
+
 def shared_export(fn):
     """``(arrays, done)``: ``fn()``'s arrays, computed ONCE per node when several data-
     parallel ranks share it (torch.distributed initialised, more than one rank on this
@@ -176,6 +209,7 @@ class DeviceGraph:
         self.root_rows = None  # optional candidate -> row map of the root sampler (node-type subset)
         self.features = None   # optional dense node feature table [N, D] (from_engine)
         self.labels = None     # optional label table (from_engine)
+        self.sparse = {}       # optional sparse feature columns: name -> (indptr [N+1], values [nnz]) int64
         self.rng = torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
         self._cpu_gen = torch.Generator(device="cpu")
         self._cpu_gen.manual_seed(int(seed))
@@ -217,7 +251,7 @@ class DeviceGraph:
 
     @classmethod
     def from_engine(cls, engine=None, node_type=-1, features=(), feature_dims=(), label=None, label_dim=None,
-                    feature_dtype=torch.bfloat16, seed=0, device="cuda", share=False):
+                    feature_dtype=torch.bfloat16, seed=0, device="cuda", share=False, sparse_features=()):
         """Upload the engine's local graph shard to HBM.
 
         The C++ engine's columnar store (``csrc/graph``) is already a per-(row, edge type)
@@ -232,17 +266,35 @@ class DeviceGraph:
 
         ``share=True`` (every data-parallel rank calls this together, as the estimator's
         device path does): local rank 0 exports once into /dev/shm and every local rank
-        uploads from the shared read-only mapping (:func:`shared_export`)."""
+        uploads from the shared read-only mapping (:func:`shared_export`).
+
+        ``sparse_features``: names of sparse (id-list) node features kept in HBM as one CSR
+        per name over the rows, ``graph.sparse[name] = (indptr int64 [N + 1], values int64
+        [nnz])``; a row without the feature has an empty segment (the lookup applies the
+        default id: ``ops/mp_ops.py node_bag``)."""
         from euler_amd.ops import base
 
         eng = engine if engine is not None else base.get_engine()
         names = [] if not features else ([features] if isinstance(features, (str, int)) else list(features))
         dims = [] if not features else ([feature_dims] if isinstance(feature_dims, int) else list(feature_dims))
+        sp_names = [] if sparse_features in (None, -1, ()) else (
+            [sparse_features] if isinstance(sparse_features, (str, int)) else list(sparse_features))
+        if sp_names and eng is not base.get_engine():
+            raise ValueError("sparse_features are read through the process's graph engine (initialize_graph)")
         if getattr(eng, "mode", "local") != "local":
-            return cls._from_shards(eng, node_type, names, dims, label, label_dim, feature_dtype, seed, device)
+            g = cls._from_shards(eng, node_type, names, dims, label, label_dim, feature_dtype, seed, device)
+            if sp_names:
+                g._set_sparse(sp_names, _export_sparse(g.ids, sp_names))
+            return g
+
         # data-parallel ranks on one node: local rank 0 exports once into /dev/shm, every rank
         # maps it (host memory does not grow with the number of ranks)
-        export = (lambda: _export_local(eng, names, dims, label, label_dim))
+        def export():
+            out = _export_local(eng, names, dims, label, label_dim)
+            if sp_names:
+                out.update(_export_sparse(out["ids"], sp_names))
+            return out
+
         arrays, done = shared_export(export) if share else (export(), lambda: None)
         try:
             ids = np.array(arrays["ids"])
@@ -254,10 +306,17 @@ class DeviceGraph:
                 g.features = _upload(arrays["features"], torch.float32, device).view(len(ids), -1).to(feature_dtype)
             if label is not None:
                 g.labels = _upload(arrays["labels"], torch.float32, device).view(len(ids), -1)
+            g._set_sparse(sp_names, arrays)
         finally:
             del arrays
             done()
         return g
+
+    def _set_sparse(self, names, arrays):
+        """upload the host CSR arrays of :func:`_export_sparse` as ``self.sparse``"""
+        for k, nm in enumerate(names):
+            self.sparse[nm] = (_upload(arrays["sp%d_indptr" % k], torch.int64, self.device),
+                               _upload(arrays["sp%d_values" % k], torch.int64, self.device))
 
     @classmethod
     def _from_shards(cls, eng, node_type, names, dims, label, label_dim, feature_dtype, seed, device):

@@ -8,7 +8,8 @@ encoders.py:496-541`` (the corrupted view permutes the per-root positions of the
 sample tree, one permutation shared by every root).
 
 One step on the device: the roots and the fan-out tree drawn from the HBM graph (alias
-tables, one Philox stream per hop), the dense features gathered once, the user's own
+tables, one Philox stream per hop), the node inputs (dense features, id embedding,
+sparse-feature embedding bags: ``models/node_inputs.py``) read once, the user's own
 aggregators run on the real and the shuffled tree, the discriminator and the loss,
 backward and one flat optimizer launch; several steps per hipGraph replay
 (:class:`~euler_amd.models.captured.CapturedTrainer`).
@@ -20,7 +21,7 @@ import torch.nn.functional as F
 
 from euler_amd.models.captured import CapturedTrainer
 from euler_amd.models.gae_trainer import _type_ids
-from euler_amd.ops import mp_ops
+from euler_amd.models.node_inputs import DeviceNodeInputs
 
 __all__ = ["DgiTrainer"]
 
@@ -33,16 +34,13 @@ class DgiTrainer(CapturedTrainer):
 
         enc = getattr(model, "_target_encoder", None)
         ne = getattr(enc, "_node_encoder", None)
-        if not isinstance(enc, ShuffleSageEncoder) or ne is None or ne.use_id or ne.use_sparse_feature or \
-                not ne.use_feature:
-            raise ValueError("DgiTrainer trains DGI over dense node features (no id / sparse-feature embeddings)")
-        if graph.features is None:
-            raise ValueError("the device graph needs the encoder's dense features (DeviceGraph.from_engine)")
+        if not isinstance(enc, ShuffleSageEncoder) or ne is None:
+            raise ValueError("DgiTrainer trains DGI (a ShuffleSageEncoder target encoder)")
+        self.inputs = DeviceNodeInputs(ne, graph)
         self.enc, self.graph = enc, graph
         self.B = int(batch_size)
         self.types = [_type_ids(m) for m in enc.metapath]
         self.fanouts = [int(f) for f in enc.fanouts]
-        self.features = graph.features
         self.acc = torch.zeros(2, dtype=torch.float64, device=graph.device)  # correct, total
         super().__init__(model, graph, graph.device, optimizer, learning_rate)
 
@@ -55,8 +53,7 @@ class DgiTrainer(CapturedTrainer):
         return hops
 
     def _features(self, rows):
-        x = mp_ops.gather(self.features, rows.clamp(min=0)).float()
-        return x * (rows >= 0).unsqueeze(1).to(x.dtype)  # the reference's default node: zeros
+        return self.inputs(rows)  # -1: the reference's default node (zeros / the default id)
 
     def _shuffle(self, hidden):
         """ShuffleSageEncoder.shuffle_tensors with the permutation drawn as an argsort of
@@ -73,7 +70,7 @@ class DgiTrainer(CapturedTrainer):
             return
         state = self.graph.rng.clone()
         with torch.no_grad():
-            self._logits(torch.zeros(self.B, dtype=torch.long, device=self.features.device))
+            self._logits(torch.zeros(self.B, dtype=torch.long, device=self.graph.device))
         self.graph.rng.copy_(state)
 
     def _logits(self, roots):

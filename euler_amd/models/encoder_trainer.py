@@ -1,7 +1,9 @@
 """Device-path training of the *encoder* models — GeniePath (``GenieEncoder``), any
 ``SuperviseModel`` whose ``_encoder`` is a ``GCNEncoder``, LGCN (``LGCEncoder``,
 :class:`LgcnTrainer`) and ``SuperviseSolution`` over a ``SageEncoder``
-(:class:`SolutionTrainer`) — under ``NodeEstimator(device_graph=True)``.
+(:class:`SolutionTrainer`) — under ``NodeEstimator(device_graph=True)``.  Their node inputs
+(dense features, id embedding, sparse-feature embedding bags: ``ShallowEncoder``) are read
+from the HBM graph by :class:`~euler_amd.models.node_inputs.DeviceNodeInputs`.
 
 Reference: ``examples/geniepath/geniepath.py:26-49``, ``tf_euler/python/utils/
 encoders.py:174-291`` (``get_multi_hop_neighbor`` node sets and sparse adjacencies, the
@@ -25,12 +27,19 @@ import torch
 from euler_amd.dataflow.device_flow import DeviceFullFlow
 from euler_amd.models.captured import CapturedTrainer
 from euler_amd.models.full_trainer import FullFlowTrainer
+from euler_amd.models.node_inputs import DeviceNodeInputs
 from euler_amd.ops import mp_ops
 
 __all__ = ["EncoderFlowTrainer", "LgcnTrainer", "SolutionTrainer", "UnsupSolutionTrainer"]
 
 
 class EncoderFlowTrainer(FullFlowTrainer):
+    needs_dense_features = False
+
+    def __init__(self, model, graph, *args, **kw):
+        self.inputs = DeviceNodeInputs(model._encoder._node_encoder, graph)
+        super().__init__(model, graph, *args, **kw)
+
     @classmethod
     def from_model(cls, model, graph, batch_size, optimizer="adam", learning_rate=0.01, **kw):
         import euler_amd.ops.graph_api as ge
@@ -38,9 +47,8 @@ class EncoderFlowTrainer(FullFlowTrainer):
 
         enc = getattr(model, "_encoder", None)
         ne = getattr(enc, "_node_encoder", None)
-        if not isinstance(enc, GCNEncoder) or ne is None or ne.use_id or ne.use_sparse_feature or \
-                not ne.use_feature:
-            raise ValueError("EncoderFlowTrainer trains GCNEncoder / GenieEncoder models over dense features")
+        if not isinstance(enc, GCNEncoder) or ne is None:
+            raise ValueError("EncoderFlowTrainer trains GCNEncoder / GenieEncoder models")
         masks = []
         for m in enc.metapath:
             ids = None if m is None else [int(t) for t in np.asarray(ge.get_edge_type_id(m)).reshape(-1)]
@@ -51,10 +59,7 @@ class EncoderFlowTrainer(FullFlowTrainer):
         return tr
 
     def _node_features(self, rows):
-        ne = self.model._encoder._node_encoder
-        x = mp_ops.gather(self.features, rows.clamp(min=0)).float()
-        x = x * (rows >= 0).unsqueeze(1).to(x.dtype)
-        return ne.dense(x) if ne.combiner == "add" else x
+        return self.inputs(rows)
 
     def _forward(self, roots):
         from euler_amd.ops.graph_api import SparseTensor
@@ -113,12 +118,15 @@ class LgcnTrainer(FullFlowTrainer):
 
 class SolutionTrainer(FullFlowTrainer):
     """``solution.SuperviseSolution`` (reference ``euler_estimator`` solution API,
-    ``examples/solution/run_solution.py``) over a dense-feature ``SageEncoder``, labels from
+    ``examples/solution/run_solution.py``) over a ``SageEncoder``, labels from
     a dense feature (``GetLabelFromFea``), the default sigmoid loss: the fan-out tree drawn
     per hop on the HBM graph (Philox stream 4 + h; ``-1`` for a node without an out-edge,
-    zero features like the engine's default node), features gathered once, the encoder's own
+    zero features / the default id like the engine's default node), the node inputs read
+    once per hop (``DeviceNodeInputs``: dense, id and sparse-feature columns), the encoder's own
     aggregators (``SageEncoder._aggregate``), the solution's ``logit_fn``, the fused loss +
     F1 counts; several steps per hipGraph."""
+
+    needs_dense_features = False
 
     @classmethod
     def from_model(cls, model, graph, batch_size, optimizer="adam", learning_rate=0.01, **kw):
@@ -129,11 +137,11 @@ class SolutionTrainer(FullFlowTrainer):
         enc = getattr(model, "encoder", None)
         ne = getattr(enc, "_node_encoder", None)
         if not isinstance(model, S.SuperviseSolution) or type(enc) is not SageEncoder or ne is None or \
-                ne.use_id or ne.use_sparse_feature or not ne.use_feature or model.loss_fn is not S.sigmoid_loss or \
-                not isinstance(model.get_label_fn, S.GetLabelFromFea):
-            raise ValueError("SolutionTrainer trains SuperviseSolution(GetLabelFromFea, dense-feature SageEncoder, "
-                             "logit_fn) with the default sigmoid loss")
+                model.loss_fn is not S.sigmoid_loss or not isinstance(model.get_label_fn, S.GetLabelFromFea):
+            raise ValueError("SolutionTrainer trains SuperviseSolution(GetLabelFromFea, SageEncoder, logit_fn) "
+                             "with the default sigmoid loss")
         tr = cls.__new__(cls)
+        tr.inputs = DeviceNodeInputs(ne, graph)
         tr.types = []
         for m in enc.metapath:
             ids = [int(t) for t in np.asarray(ge.get_edge_type_id(m)).reshape(-1)]
@@ -148,11 +156,7 @@ class SolutionTrainer(FullFlowTrainer):
         for i, (f, et) in enumerate(zip(enc.fanouts, self.types)):
             hops.append(self.graph.sample_neighbor(hops[-1], int(f), edge_types=et, default=-1,
                                                    stream_id=4 + i).long().reshape(-1))
-        hidden = []
-        for rows in hops:
-            x = mp_ops.gather(self.features, rows.clamp(min=0)).float()
-            hidden.append(x * (rows >= 0).unsqueeze(1).to(x.dtype))
-        emb = enc._aggregate(hidden)
+        emb = enc._aggregate([self.inputs(rows) for rows in hops])
         return self.model.logit_fn(emb).float(), None
 
 
@@ -160,8 +164,8 @@ def _check_sage_encoder(enc):
     from euler_amd.utils.encoders import SageEncoder
 
     ne = getattr(enc, "_node_encoder", None)
-    if type(enc) is not SageEncoder or ne is None or ne.use_id or ne.use_sparse_feature or not ne.use_feature:
-        raise ValueError("the solution device paths take dense-feature SageEncoders")
+    if type(enc) is not SageEncoder or ne is None:
+        raise ValueError("the solution device paths take SageEncoders")
     return ne
 
 
@@ -170,25 +174,21 @@ def _type_list(ge, et):
     return None if any(t < 0 for t in ids) else ids
 
 
-def _sage_tree_encode(enc, graph, features, types, roots, stream_base):
-    """SageEncoder.forward on the HBM graph: per-hop draws (Philox stream_base + h), one
-    feature gather per hop, the encoder's aggregators"""
+def _sage_tree_encode(enc, graph, inputs, types, roots, stream_base):
+    """SageEncoder.forward on the HBM graph: per-hop draws (Philox stream_base + h), the
+    node inputs of every hop (``inputs``: a DeviceNodeInputs), the encoder's aggregators"""
     hops = [roots.reshape(-1).long()]
     for i, (f, et) in enumerate(zip(enc.fanouts, types)):
         hops.append(graph.sample_neighbor(hops[-1], int(f), edge_types=et, default=-1,
                                           stream_id=stream_base + i).long().reshape(-1))
-    hidden = []
-    for rows in hops:
-        x = mp_ops.gather(features, rows.clamp(min=0)).float()
-        hidden.append(x * (rows >= 0).unsqueeze(1).to(x.dtype))
-    return enc._aggregate(hidden)
+    return enc._aggregate([inputs(rows) for rows in hops])
 
 
 class UnsupSolutionTrainer(CapturedTrainer):
     """``solution.UnsuperviseSolution`` (reference ``base_unsupervise.py:27-73``) with
-    dense-feature ``SageEncoder`` target / context encoders, ``SamplePosWithTypes``
-    positives and single-type ``SampleNegWithTypes`` negatives: roots, positives and
-    negatives drawn on the HBM graph, both encoders' trees built there, the solution's own
+    ``SageEncoder`` target / context encoders (dense, id and sparse-feature inputs),
+    ``SamplePosWithTypes`` positives and single-type ``SampleNegWithTypes`` negatives: roots,
+    positives and negatives drawn on the HBM graph, both encoders' trees built there, the solution's own
     ``logit_fn`` and ``loss_fn``, MRR on the device; several steps per hipGraph."""
 
     metric_name = "mrr"
@@ -203,17 +203,16 @@ class UnsupSolutionTrainer(CapturedTrainer):
         ne_c = _check_sage_encoder(model.context_encoder)
         pos_fn, neg_fn = model.pos_sample_fn, model.neg_sample_fn
         if not isinstance(pos_fn, S.SamplePosWithTypes) or not isinstance(neg_fn, S.SampleNegWithTypes) or \
-                len(neg_fn.neg_type) != 1 or list(ne_c.feature_idx) != list(ne.feature_idx):
+                len(neg_fn.neg_type) != 1 or ne_c.use_feature != ne.use_feature or \
+                (ne.use_feature and list(ne_c.feature_idx) != list(ne.feature_idx)):
             raise ValueError("UnsupSolutionTrainer takes SamplePosWithTypes / single-type SampleNegWithTypes "
                              "samplers and encoders over the same dense features")
-        if graph.features is None:
-            raise ValueError("the device graph needs the encoders' dense features (DeviceGraph.from_engine)")
+        self.t_inputs, self.c_inputs = DeviceNodeInputs(ne, graph), DeviceNodeInputs(ne_c, graph)
         self.graph, self.B = graph, int(batch_size)
         self.P, self.K = int(pos_fn.num_pos), int(neg_fn.num_negs)
         self.pos_types = _type_list(ge, pos_fn.edge_type)
         self.t_types = [_type_list(ge, m) for m in model.target_encoder.metapath]
         self.c_types = [_type_list(ge, m) for m in model.context_encoder.metapath]
-        self.features = graph.features
         nt = neg_fn.neg_type[0]
         tid = -1 if nt in (None, -1, "-1") else int(np.asarray(ge.get_node_type_id(nt)).reshape(-1)[0])
         _, _, nw = ge.get_engine().export_nodes()
@@ -227,15 +226,15 @@ class UnsupSolutionTrainer(CapturedTrainer):
             return
         state = self.graph.rng.clone()
         with torch.no_grad():
-            self._logits(torch.zeros(self.B, dtype=torch.long, device=self.features.device))
+            self._logits(torch.zeros(self.B, dtype=torch.long, device=self.graph.device))
         self.graph.rng.copy_(state)
 
     def _logits(self, src):
         m, g, B = self.model, self.graph, self.B
         pos = g.sample_neighbor(src, self.P, edge_types=self.pos_types, default=-1, stream_id=4).long().reshape(-1)
         neg = self.neg_sampler.sample_node(B * self.K, stream_id=5).long()
-        emb = _sage_tree_encode(m.target_encoder, g, self.features, self.t_types, src, 10).view(B, 1, -1)
-        ctx = _sage_tree_encode(m.context_encoder, g, self.features, self.c_types, torch.cat([pos, neg]), 20)
+        emb = _sage_tree_encode(m.target_encoder, g, self.t_inputs, self.t_types, src, 10).view(B, 1, -1)
+        ctx = _sage_tree_encode(m.context_encoder, g, self.c_inputs, self.c_types, torch.cat([pos, neg]), 20)
         d = ctx.shape[-1]
         self._samples = (src, pos, neg)
         return m.logit_fn(emb, ctx[: B * self.P].view(B, self.P, d), ctx[B * self.P:].view(B, self.K, d))

@@ -64,6 +64,9 @@ def infer_flow(owner, graph, masks, self_loops, n):
 
 class FullFlowTrainer(CapturedTrainer):
     metric_name = "f1"
+    # False: a subclass builds its node inputs itself (models/node_inputs.py: id / sparse-feature
+    # embeddings, possibly no dense column at all)
+    needs_dense_features = True
 
     def __init__(self, model, graph, batch_size, masks, add_self_loops=True, features=None, labels=None,
                  optimizer="adam", learning_rate=0.01, caps=None, flow=None):
@@ -72,9 +75,9 @@ class FullFlowTrainer(CapturedTrainer):
         self.B = int(batch_size)
         feats = features if features is not None else graph.features
         labs = labels if labels is not None else graph.labels
-        if feats is None or labs is None:
+        if (feats is None and self.needs_dense_features) or labs is None:
             raise ValueError("the device graph needs dense features and labels (DeviceGraph.from_engine)")
-        self.features = feats.to(graph.device)
+        self.features = None if feats is None else feats.to(graph.device)
         self.labels = labs.to(graph.device).float()
         # the full-neighbourhood flow by default; a given flow (DeviceSageFlow for models on
         # the sampled SageDataFlow whose convolutions are not the fused SAGE kernels)

@@ -26,7 +26,7 @@ import torch
 from euler_amd.ops._native import hip, use_hip
 
 __all__ = ["SegmentIndex", "gather", "gather_sum", "scatter_add", "scatter_mean", "scatter_max", "scatter_softmax",
-           "scatter_", "segment_index", "embedding_bag", "weighted_aggregate"]
+           "scatter_", "segment_index", "embedding_bag", "weighted_aggregate", "node_bag"]
 
 
 class SegmentIndex:
@@ -390,6 +390,126 @@ def embedding_bag(table, ids, bag_of, num_bags, combiner="sum", weights=None):
         return _EmbeddingBag.apply(table, indptr, ids.contiguous(), w.contiguous(), bag_of.contiguous())
     vals = table[ids] * w.unsqueeze(1).to(table.dtype)
     return torch.zeros((num_bags, table.shape[1]), dtype=table.dtype, device=table.device).index_add(0, bag_of, vals)
+
+
+_NODE_BAG_MODES = {"bag_sum": 0, "bag_mean": 1, "id": 2}
+
+
+def _node_bag_map(v, V, hash):
+    """table row of id ``v`` (layers.Embedding._rows / HashEmbedding._rows)"""
+    if hash:
+        return ((v * 0x9E3779B1) & 0x7FFFFFFF) % V
+    return torch.where((v < 0) | (v >= V), torch.full_like(v, V - 1), v)
+
+
+def _node_bag_index(rows, index, mode, V, hash):
+    """host-sized twin of the kernels' indexing: (table row of every looked-up id [m], the
+    output row it belongs to [m], ids per output row [n]) in CSR order"""
+    n = rows.numel()
+    default = torch.full((n,), V - 1, dtype=torch.long, device=rows.device)
+    if mode == "id":
+        ok = rows >= 0
+        v = rows
+        if index is not None:
+            ok = ok & (rows < index.numel())
+            v = index.long()[torch.where(ok, rows, torch.zeros_like(rows))] if index.numel() else default
+        ids = torch.where(ok, v, default)
+        return _node_bag_map(ids, V, hash), torch.arange(n, device=rows.device), torch.ones_like(rows)
+    indptr, values = index
+    N = indptr.numel() - 1
+    ok = (rows >= 0) & (rows < N)
+    safe = torch.where(ok, rows, torch.zeros_like(rows))
+    a = indptr[safe] if N else torch.zeros_like(rows)
+    ln = torch.where(ok, (indptr[safe + 1] - a) if N else torch.zeros_like(rows), torch.zeros_like(rows))
+    empty = ln <= 0
+    cnt = torch.where(empty, torch.ones_like(ln), ln)  # an empty bag holds the default id
+    bag = torch.repeat_interleave(torch.arange(n, device=rows.device), cnt)
+    off = torch.arange(bag.numel(), device=rows.device) - torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt)
+    src = (a[bag] + off).clamp(max=max(values.numel() - 1, 0))
+    ids = torch.where(empty[bag], default[bag], values[src] if values.numel() else default[bag])
+    return _node_bag_map(ids, V, hash), bag, cnt
+
+
+def _node_bag_cpu(table, rows, index, mode, hash):
+    V, D = table.shape
+    tr, bag, cnt = _node_bag_index(rows, index, mode, V, hash)
+    out = torch.zeros((rows.numel(), D), dtype=table.dtype, device=table.device).index_add(0, bag, table[tr])
+    if mode == "bag_mean":
+        out = out * (1.0 / cnt.to(table.dtype)).unsqueeze(1)
+    return out
+
+
+class _NodeBag(torch.autograd.Function):
+    """the two launches of csrc/hip/node_embed.hip: the forward writes columns
+    [col, col + D) of ``out`` in place; the backward adds into a zeroed [V, D] gradient"""
+
+    @staticmethod
+    def forward(ctx, table, out, rows, indptr, values, node_ids, mode, hash, col):
+        ctx.mark_dirty(out)
+        ctx.save_for_backward(rows, indptr, values, node_ids)
+        ctx.cfg = (tuple(table.shape), int(mode), bool(hash), int(col))
+        hip().node_bag_fwd(rows, indptr, values, node_ids, table.contiguous(), out, int(col), int(mode), bool(hash))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, indptr, values, node_ids = ctx.saved_tensors
+        (V, D), mode, hash, col = ctx.cfg
+        g = g.contiguous().float()
+        d_table = d_out = None
+        if ctx.needs_input_grad[0]:
+            d_table = torch.zeros((V, D), dtype=torch.float32, device=g.device)  # a fill kernel: capturable
+            hip().node_bag_bwd_(d_table, rows, indptr, values, node_ids, g, col, mode, hash)
+        if ctx.needs_input_grad[1]:
+            d_out = g.clone()  # the overwritten columns carry nothing back to the buffer
+            d_out[:, col: col + D] = 0
+        return d_table, d_out, None, None, None, None, None, None, None
+
+
+def node_bag(table, rows, csr_or_ids, mode="bag_sum", hash=False, out=None, col=0):
+    """Embedding rows of graph rows, straight from the device graph (``DeviceGraph.sparse`` /
+    ``DeviceGraph.ids``): ``[n, D]``, or columns ``[col, col + D)`` of ``out [n, ld]`` (the
+    other columns are left alone; ``out`` is returned).
+
+    * ``mode="bag_sum" | "bag_mean"``: ``csr_or_ids = (indptr [N + 1], values [nnz])``; the
+      sum (mean: times ``1 / count``) of ``table[map(id)]`` over the row's ids in CSR order,
+      fp32.  An empty bag, a negative row and a row past ``N`` are a bag of the default id
+      ``V - 1`` (the engine's ``default_values = max_id + 1`` and its default node).
+    * ``mode="id"``: ``csr_or_ids`` is the int64 id column ``[N]`` or ``None`` (ids = rows);
+      ``table[map(id)]``, the default id for a negative row.
+    * ``map(v) = v`` for ``0 <= v < V`` else ``V - 1``; with ``hash`` the multiplicative
+      hash of ``HashEmbedding``.
+
+    On the GPU: one fixed-shape launch forward (no host read: capturable) and one backward
+    whose fp32 atomics arrive in any order: the table gradient is NOT bit-reproducible from
+    run to run (zero addends, e.g. of ``-1`` padding rows, are skipped).  CPU tensors take a
+    pure-torch twin with the same semantics (host-sized intermediates)."""
+    if mode not in _NODE_BAG_MODES:
+        raise ValueError("node_bag: mode must be one of %s" % sorted(_NODE_BAG_MODES))
+    if table.dim() != 2:
+        raise ValueError("node_bag: table must be [V, D]")
+    rows = rows.reshape(-1).long()
+    D = table.shape[1]
+    if out is not None and (out.dim() != 2 or out.shape[0] != rows.numel() or col < 0 or col + D > out.shape[1]):
+        raise ValueError("node_bag: out must be [n, ld] with col + D <= ld")
+    if mode == "id":
+        index = None if csr_or_ids is None else csr_or_ids.reshape(-1)
+        parts = (None, None, index)
+    else:
+        index = (csr_or_ids[0].reshape(-1), csr_or_ids[1].reshape(-1))
+        parts = index + (None,)
+    if use_hip(table, rows):
+        if table.dtype != torch.float32:
+            raise ValueError("node_bag: the table must be fp32")
+        if out is None:
+            out, col = torch.empty((rows.numel(), D), dtype=torch.float32, device=table.device), 0
+        parts = [None if t is None else t.long().contiguous() for t in parts]
+        return _NodeBag.apply(table, out, rows.contiguous(), *parts, _NODE_BAG_MODES[mode], bool(hash), int(col))
+    res = _node_bag_cpu(table, rows, index, mode, bool(hash))
+    if out is None:
+        return res
+    out[:, col: col + D] = res
+    return out
 
 
 def scatter_softmax(logits, indices, size=None):

@@ -36,6 +36,21 @@ def _hidden(a, out):
     return [a.hidden_dim] * a.layers + [out]
 
 
+def _sparse_kw(a, ds):
+    """--use_sparse_feature / --use_id / --embedding_dim as encoder keyword arguments
+    (reference examples/geniepath/geniepath.py:31, examples/dgi/dgi.py:73); nothing by default"""
+    kw = {}
+    if getattr(a, "use_sparse_feature", False):
+        if getattr(ds, "sparse_fea_idx", None) is None:
+            raise SystemExit("--use_sparse_feature: dataset %r has no sparse feature" % ds.name)
+        kw.update(sparse_feature_idx=ds.sparse_fea_idx, sparse_feature_max_id=ds.sparse_fea_max_id)
+    if getattr(a, "use_id", False):
+        kw.update(use_id=True)
+    if kw:
+        kw.update(embedding_dim=a.embedding_dim)
+    return kw
+
+
 def _mp(a, n=None):
     """metapath: the training edges for run_mode train, every edge type otherwise (the
     reference's run_graphsage.py:53-57 — evaluation reaches the held-out nodes, whose
@@ -84,7 +99,8 @@ def _models():
                                                         ds.label_idx, ds.label_dim, K=a.K)),
         "geniepath": ("cora", "node", lambda a, ds: Z.GeniePath(a.hidden_dim, _mp(a), ds.label_idx, ds.label_dim,
                                                                 feature_idx=ds.feature_idx, feature_dim=F(ds),
-                                                                head_num=a.head_num)),
+                                                                head_num=a.head_num, max_id=ds.max_node_id,
+                                                                **_sparse_kw(a, ds))),
         "lgcn": ("cora", "node", lambda a, ds: Z.LGCN(a.hidden_dim, [_first(ds.train_edge_type)], ds.label_idx,
                                                       ds.label_dim, feature_idx=ds.feature_idx, feature_dim=F(ds))),
         "deepwalk": ("cora", "node", lambda a, ds: Z.DeepWalk(_first(ds.train_node_type), _first(ds.train_edge_type),
@@ -99,7 +115,8 @@ def _models():
                                                       sharded=a.sharded)),
         "dgi": ("cora", "node", lambda a, ds: Z.DGI(_first(ds.train_node_type), _first(ds.train_edge_type),
                                                     ds.max_node_id, _mp(a), a.fanouts, a.dim,
-                                                    feature_idx=ds.feature_idx, feature_dim=F(ds))),
+                                                    feature_idx=ds.feature_idx, feature_dim=F(ds),
+                                                    **_sparse_kw(a, ds))),
         "gae": ("cora", "node", lambda a, ds: Z.GraphAutoEncoder("gcn" if a.gae_encoder == "gcn" else "sage",
                                                                  _hidden(a, a.dim)[1:], a.fanouts[:a.layers - 1] or
                                                                  a.fanouts, _mp(a, a.layers - 1 or 1),
@@ -219,6 +236,11 @@ def parse_args(argv=None, model=None):
                    help="engine path: C++ batch pipeline (sampling + features into pinned slots) for "
                         "SupervisedGNN + SageDataFlow models; auto = on for GPU training")
     p.add_argument("--pipeline_workers", type=int, default=8)
+    p.add_argument("--use_sparse_feature", action="store_true",
+                   help="geniepath / dgi: add the dataset's sparse feature (e.g. cora_sparse's words) as an "
+                        "embedding-bag input of the node encoder")
+    p.add_argument("--use_id", action="store_true", help="geniepath / dgi: add a node-id embedding input")
+    p.add_argument("--embedding_dim", type=int, default=16, help="width of the id / sparse-feature embeddings")
     p.add_argument("--seed", type=int, default=None)
     return p.parse_args(argv)
 
@@ -235,6 +257,8 @@ def build(a):
     if a.model not in MODELS:
         raise SystemExit("unknown model %r; choose from %s" % (a.model, sorted(MODELS)))
     ds_name, kind, builder = MODELS[a.model]
+    if (a.use_sparse_feature or a.use_id) and a.model not in ("geniepath", "dgi"):
+        raise SystemExit("--use_sparse_feature / --use_id are accepted for geniepath and dgi")
     ds = get_dataset(a.dataset or ds_name, data_dir=a.data_dir, scale=a.scale)
     if getattr(a, "engine_shards", False):
         import torch.distributed as dist
