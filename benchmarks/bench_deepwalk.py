@@ -109,6 +109,13 @@ def main(argv=None):
     p.add_argument("--mode", choices=["graph", "static", "dynamic"], default="graph",
                    help="graph: fixed-capacity step captured in one hipGraph and replayed; static: the same "
                         "step eager; dynamic: exact-size step (host-read unique counts / all-to-all splits)")
+    p.add_argument("--sharded-graph", action="store_true",
+                   help="the graph row-sharded over the ranks too (ShardedDeviceGraph.synthetic): every hop of a "
+                        "walk and every root / negative draw is answered by the row's owner over all-to-alls; "
+                        "with --force-dist one rank runs the same exchanges")
+    p.add_argument("--walk-hops", choices=["fused", "composed"], default="fused",
+                   help="--sharded-graph: the hop kernels of csrc/hip/walk_shard.hip, or the same hops composed "
+                        "from the sharded sample_neighbor and torch passes (the comparison point)")
     p.add_argument("--eval-nodes", type=int, default=1_000_000, help="0: skip the learning-evidence run")
     p.add_argument("--eval-steps", type=int, default=3000)
     p.add_argument("--eval-lr", type=float, default=0.05)
@@ -149,7 +156,17 @@ def main(argv=None):
         free = torch.cuda.mem_get_info(dev)[0]
         args.optimizer = "adam" if need < 0.8 * free else "adagrad"
     t0 = time.time()
-    g = DeviceGraph.synthetic(args.num_nodes, args.avg_degree, args.max_degree, seed=args.seed, device=dev)
+    if args.sharded_graph:
+        from euler_amd.graph.sharded_graph import ShardedDeviceGraph
+
+        # structure only: a 1-column feature table and one label column keep the generator's interface
+        g = ShardedDeviceGraph.synthetic(args.num_nodes, args.avg_degree, args.max_degree, feature_dim=1,
+                                         num_classes=2, seed=args.seed, device=dev, force_comm=args.force_dist)
+        if args.walk_hops == "composed":
+            g.random_walk = lambda starts, walk_len, edge_types=None, default=-1, stream_id=3, p=1.0, q=1.0: \
+                g._random_walk_composed(starts, walk_len, edge_types, default, stream_id)
+    else:
+        g = DeviceGraph.synthetic(args.num_nodes, args.avg_degree, args.max_degree, seed=args.seed, device=dev)
     g.manual_seed(args.seed * 7919 + rank)
     tr = DeepWalkTrainer(g, args.num_nodes, args.dim, args.walk_len, 1, 1, args.num_negs, args.batch, args.lr,
                          args.optimizer, seed=args.seed, force_comm=args.force_dist, static=args.mode != "dynamic",
@@ -157,7 +174,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     if rank == 0:
         gib = tr.table.nbytes() / 2 ** 30
-        print(f"[bench_deepwalk] {args.num_nodes} nodes, {g.num_edges} edges, tables+slots {gib:.1f} GiB/rank, "
+        print(f"[bench_deepwalk] {args.num_nodes} nodes, {(g.local if args.sharded_graph else g).num_edges} edges"
+              f"{' on this rank' if args.sharded_graph else ''}, tables+slots {gib:.1f} GiB/rank, "
               f"setup {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
 
     if args.mode == "graph":
@@ -182,7 +200,7 @@ def main(argv=None):
         dist.all_reduce(elt, op=dist.ReduceOp.MAX)
     el = float(elt.item())
     pairs = tr.pairs_per_step() * world * args.steps
-    tr.table.check_overflow()
+    tr.check_overflow()
     pairs_per_step, table_comm, loss_last = tr.pairs_per_step(), bool(tr.table.comm), float(tr.loss)
     peak = torch.cuda.max_memory_allocated() / 2 ** 30
     tr.release()
@@ -198,6 +216,8 @@ def main(argv=None):
             "ranks": world,
             "shared_gpu_rehearsal": bool(args.shared_gpu) or None,
             "parallelism": f"dp{world}+sharded-emb",
+            "graph": "sharded" if args.sharded_graph else "whole",
+            "walk_hops": args.walk_hops if args.sharded_graph else None,
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(el * 1e3 / args.steps, 3),

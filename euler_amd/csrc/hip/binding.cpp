@@ -600,6 +600,8 @@ void register_gcn_ops(pybind11::module& m);
 void register_graph_cls_ops(pybind11::module& m);
 // binding_node_embed.cpp: node rows -> embedding bags (sparse-feature / id inputs)
 void register_node_embed_ops(pybind11::module& m);
+// binding_walk_shard.cpp: the hop kernels of random walks over the row-sharded graph
+void register_walk_shard_ops(pybind11::module& m);
 
 PYBIND11_MODULE(_hip_ops, m) {
   register_gnn_ops(m);
@@ -607,6 +609,7 @@ PYBIND11_MODULE(_hip_ops, m) {
   register_gcn_ops(m);
   register_graph_cls_ops(m);
   register_node_embed_ops(m);
+  register_walk_shard_ops(m);
   m.doc() = "euler_amd hand-written CDNA4 (gfx950) HIP kernels";
   m.attr("arch") = "gfx950";
   m.def("rng_advance", &rng_advance);

@@ -157,6 +157,17 @@ int64_t eh_route_chunks(int64_t n);
 hipError_t eh_route_by_owner(const int64_t* ids, int64_t n, int W, int64_t C, int self_rank, int32_t* cnt,
                              int64_t* pos, int64_t* send, int32_t* overflow, hipStream_t s);
 
+// walk_shard.hip (one hop of a random walk over the row-sharded graph)
+hipError_t eh_walk_keys(const int32_t* starts, int64_t n, int64_t num_rows, int64_t R, int64_t ticket0, int64_t cols,
+                        int32_t* out, int64_t* keys, hipStream_t s);
+hipError_t eh_walk_step_owner(const int64_t* req, int64_t m, int64_t R, int W, const int64_t* indptr,
+                              const int32_t* nbr, const float* cumw, int64_t local_rows, int num_types,
+                              uint32_t mask, int hop, const int64_t* rng, uint64_t stream_id, int32_t* ans,
+                              hipStream_t s);
+hipError_t eh_walk_unroute(const int32_t* back, int64_t m, const int64_t* pos, int64_t n, int32_t default_row,
+                           int64_t num_rows, int64_t R, int64_t ticket0, int64_t cols, int64_t col, int32_t* out,
+                           int64_t* keys, hipStream_t s);
+
 // unique.hip (K8: hash unique, first-occurrence order)
 hipError_t eh_unique_init(void* keys, int32_t* minpos, int64_t cap, hipStream_t s);
 hipError_t eh_unique_insert(const int64_t* x, int64_t n, void* keys, int32_t* minpos, int64_t cap, int32_t* slot,

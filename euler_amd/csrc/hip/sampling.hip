@@ -96,11 +96,9 @@ __global__ __launch_bounds__(256) void random_walk_kernel(
     int32_t nxt = default_row;
     const uint32_t mask = step_masks[s];
     if (cur >= 0 && cur < num_rows) {
-      const uint4_t r = Philox::gen(static_cast<uint64_t>(rng[0]),
-                                    (static_cast<uint64_t>(rng[1]) << 8) ^ stream_id,
-                                    static_cast<uint64_t>(i) * 1024u + s);
-      const int64_t base = cur * num_types;
+      const uint4_t r = walk_philox(rng, stream_id, static_cast<uint64_t>(i), s);
       if (biased) {
+        const int64_t base = cur * num_types;
         const bool has_prev = prev >= 0 && prev < num_rows;
         float tot = 0.f;
         // `picked` (not nxt == default_row) marks a draw: the default may be a valid row
@@ -138,35 +136,7 @@ __global__ __launch_bounds__(256) void random_walk_kernel(
           if (pass == 0 && !(tot > 0.f)) break;
         }
       } else {
-        float tot = 0.f;
-        for (int t = 0; t < num_types; ++t) {
-          if (!((mask >> t) & 1u)) continue;
-          const int64_t a = indptr[base + t], b = indptr[base + t + 1];
-          if (b > a) tot += cumw[b - 1];
-        }
-        if (tot > 0.f) {
-          float u = u01(r[0]) * tot;
-          int64_t lo = 0, hi = 0;
-          float g = 0.f;
-          for (int t = 0; t < num_types; ++t) {
-            if (!((mask >> t) & 1u)) continue;
-            const int64_t a = indptr[base + t], b = indptr[base + t + 1];
-            if (b <= a) continue;
-            g = cumw[b - 1];
-            lo = a;
-            hi = b;
-            if (u < g) break;
-            u -= g;
-          }
-          const float v = u01(r[1]) * g;
-          int64_t a = lo, b = hi - 1;
-          while (a < b) {
-            const int64_t m = (a + b) >> 1;
-            if (cumw[m] > v) b = m;
-            else a = m + 1;
-          }
-          nxt = nbr[a];
-        }
+        nxt = walk_draw_unbiased(indptr, nbr, cumw, num_types, mask, cur, r, default_row);
       }
     }
     out[i * (walk_len + 1) + s + 1] = nxt;

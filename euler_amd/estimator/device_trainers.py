@@ -158,13 +158,20 @@ def _sharded_unsup(model) -> bool:
             and len(gnn.convs) == 2 and all(isinstance(c, SAGEConv) for c in gnn.convs))
 
 
+def _sharded_walks(model) -> bool:
+    """the ``skipgram_walks`` models: DeepWalk / Node2Vec, and LINE with separate target and
+    context tables (first-order LINE shares one table between both roles)"""
+    return _cls("BaseNode2Vec", "Line")(model) and not _is_line1(model)
+
+
 def sharded_supported(model) -> bool:
     """supervised models on the sampled ``SageDataFlow`` or the full-neighbourhood
-    ``GCNDataFlow`` (any convolution, no stores), and the unsupervised 2-hop GraphSAGE"""
+    ``GCNDataFlow`` (any convolution, no stores), the unsupervised 2-hop GraphSAGE, and the
+    skip-gram walk models (DeepWalk / Node2Vec with p = q = 1, second-order LINE)"""
     from euler_amd.dataflow import dataflows as D
 
     gnn = getattr(model, "gnn", None)
-    if _sharded_unsup(model):
+    if _sharded_unsup(model) or _sharded_walks(model):
         return True
     return (gnn is not None and hasattr(gnn, "feature_idx") and hasattr(model, "label_idx")
             and not hasattr(model, "context_gnn") and not has_store_encoder(model)
@@ -174,21 +181,49 @@ def sharded_supported(model) -> bool:
 def build_sharded_trainer(est, model, first):
     """a graph larger than one GPU's HBM: every rank uploads only its rows (r % W) of the
     CSR, features and labels (graph/sharded_graph.py) and the neighbour draws, features and
-    labels cross the ranks over all-to-all (models/full_trainer.py ShardedFlowTrainer)"""
+    labels cross the ranks over all-to-all (models/full_trainer.py ShardedFlowTrainer; the
+    skip-gram walk models: models/deepwalk_step.py over ShardedDeviceGraph.random_walk)"""
     from euler_amd.graph.sharded_graph import ShardedDeviceGraph
     from euler_amd.models.full_trainer import ShardedFlowTrainer
 
     if not sharded_supported(model):
         raise NoDeviceTrainer("device_graph_sharded=True trains supervised models on the sampled SageDataFlow or "
-                              "the full-neighbourhood GCNDataFlow, and the unsupervised GraphSAGE; "
-                              f"{type(model).__name__} is not one")
+                              "the full-neighbourhood GCNDataFlow, the unsupervised GraphSAGE, and DeepWalk / "
+                              "Node2Vec / second-order LINE (first-order LINE shares one table between the target "
+                              f"and context roles and is not supported); {type(model).__name__} is not one")
+    walks = _sharded_walks(model)
+    if walks and est.world > 1 and (float(getattr(model, "walk_p", 1)) != 1.0 or
+                                    float(getattr(model, "walk_q", 1)) != 1.0):
+        from euler_amd.graph.sharded_graph import NODE2VEC_SHARDED
+
+        raise NoDeviceTrainer(NODE2VEC_SHARDED)
     est._prepare(first, build_optimizer=False)
     c = Ctx(est, model)
-    gnn = model.gnn
+    gnn = getattr(model, "gnn", None)
     # "engine_shards": every rank's engine holds only its partitions (initialize_graph with
     # shard_idx = rank, shard_num = W): host memory per rank is 1/W of the graph
     build = ShardedDeviceGraph.from_engine_shard if est.params.get("device_graph_sharded") == "engine_shards" \
         else ShardedDeviceGraph.from_engine
+    if walks:
+        # DeepWalk / Node2Vec / LINE (second order): the walks' hops and the root / negative
+        # draws answered by the rows' owners (ShardedDeviceGraph.random_walk / sample_node),
+        # the row-sharded SGNS tables as on the whole graph; structure only, no features
+        from euler_amd.models.deepwalk_step import DeepWalkEstimatorTrainer
+
+        g = build(node_type=c.node_type(model.node_type), features=(), seed=c.seed * 7919 + est.rank,
+                  device=est.device)
+        if not g.comm:
+            # one rank holds every row: the whole-graph trainer (rows -> node ids as the
+            # sharded graph records them)
+            g.local.ids = g.ids
+            if getattr(g, "row_ids", None) is not None:
+                g.local.row_ids = g.row_ids
+            tr = DeepWalkEstimatorTrainer(model, g.local, c.batch, seed=c.seed, **c.opt_kw())
+            tr.device_trainer_kind = "skipgram_walks"
+            return tr
+        tr = DeepWalkEstimatorTrainer(model, g, c.batch, seed=c.seed, **c.opt_kw())
+        tr.device_trainer_kind = "sharded_skipgram_walks"
+        return tr
     if _sharded_unsup(model):
         # UnsupervisedGraphSage: both towers' trees, the positives and the negatives drawn
         # through the owners (models/sharded_unsup.py); one rank without collectives: the

@@ -22,6 +22,9 @@ the shards and RCCL's all-to-all over xGMI is the transport:
   sharded graph: the shards' node-weight sums pick the shard, ``graph.cc:333-403``): each
   root picks its owner from the alias table of the W shard sums, the per-owner tickets go
   through the same exchange, the owner draws that many local roots from its own alias table;
+* ``random_walk(starts, L)``: one such exchange per hop; the walkers' requests carry a ticket
+  that numbers the owner's Philox draw, and the per-hop packing / draw / scatter are the
+  kernels of ``csrc/hip/walk_shard.hip`` (p = q = 1 only);
 * features and labels: :class:`~euler_amd.graph.sharded_features.ShardedFeatures` exchanges
   (dedup, fixed capacity, zero row for ``-1``).
 
@@ -42,12 +45,15 @@ import torch.distributed as dist
 
 from euler_amd.graph.device_graph import DeviceGraph, _upload, build_alias_table, shared_export
 from euler_amd.graph.sharded_features import ShardedFeatures
-from euler_amd.ops import mp_ops
+from euler_amd.ops import gnn_ops, mp_ops
 from euler_amd.ops._native import hip, use_hip
 from euler_amd.ops.gnn_ops import route_by_owner
 from euler_amd.parallel import comm
 
-__all__ = ["ShardedDeviceGraph", "shard_csr"]
+__all__ = ["ShardedDeviceGraph", "shard_csr", "NODE2VEC_SHARDED"]
+
+NODE2VEC_SHARDED = ("node2vec-biased walks (p or q != 1) are not available on the row-sharded graph: the bias "
+                    "needs the previous row's neighbour set, which lives on another rank")
 
 
 def shard_csr(indptr, nbr, w, T: int, world: int, rank: int):
@@ -382,6 +388,60 @@ class ShardedDeviceGraph:
         if not with_weights:
             return out_nb
         return out_nb, self._back(w.view(-1, F).float(), pos, 0.0), self._back(t.view(-1, F).int(), pos, -1)
+
+    # ------------------------------------------------------------------ random walks
+    def random_walk(self, starts: torch.Tensor, walk_len: int, edge_types=None, default: int = -1,
+                    stream_id: int = 3, p: float = 1.0, q: float = 1.0) -> torch.Tensor:
+        """Walks ``[n, walk_len + 1]`` of global rows (int32) with the contract of
+        :meth:`DeviceGraph.random_walk` for ``p == q == 1``: column 0 is the start, every
+        further column one weighted draw from the previous row's out-edges over
+        ``edge_types``, made by that row's owner; a walker whose row is ``< 0``,
+        ``>= num_rows`` or has no such edge writes ``default`` from there on.
+
+        Per hop the walkers' rows go to their owners over a ``capacity(n)``-slot all-to-all,
+        the owners draw, a second all-to-all returns the draws (reference
+        random_walk_op.cc:172-291 over remote_op.cc:60-146).  On the GPU the rest of the hop
+        is three kernels (csrc/hip/walk_shard.hip): a request is ``ticket * R + row`` with
+        ``ticket = rank * n + i``, the owner's Philox counter is ``ticket * 1024 + hop``.
+        Fixed shapes and no host read: the walk records into a hipGraph.  Every rank must
+        walk the same number of rows.  A request past its owner's slots sets ``overflow``
+        and ends that walker."""
+        if float(p) <= 0.0 or float(q) <= 0.0:
+            raise ValueError("random_walk: p and q must be positive")
+        if self.world == 1 and not self.comm:
+            return self.local.random_walk(starts, walk_len, edge_types, default, stream_id, p, q)
+        if float(p) != 1.0 or float(q) != 1.0:
+            raise ValueError(NODE2VEC_SHARDED)
+        starts = starts.reshape(-1).int()
+        if not use_hip(self.local.indptr, starts):
+            return self._random_walk_composed(starts, walk_len, edge_types, default, stream_id)
+        n, L, W = starts.numel(), int(walk_len), self.world
+        if L >= 1024:
+            raise ValueError("random_walk: at most 1023 hops")
+        R = gnn_ops.walk_key_space(self.num_rows, W, n)
+        mask, t0, C = self._mask(edge_types), self.rank * n, self.capacity(n)
+        out = torch.empty((n, L + 1), dtype=torch.int32, device=self.device)
+        keys = gnn_ops.walk_keys(starts, out, self.num_rows, R, W, t0)
+        for s in range(L):
+            pos, send = route_by_owner(keys, W, C, self.overflow)
+            ans = gnn_ops.walk_step_owner(self._a2a(send[: W * C]), R, W, self.local, mask, s, stream_id)
+            keys = gnn_ops.walk_unroute(self._a2a(ans), pos, out, s + 1, default, self.num_rows, R, W, t0)
+        return out
+
+    def _random_walk_composed(self, starts: torch.Tensor, walk_len: int, edge_types=None, default: int = -1,
+                              stream_id: int = 3) -> torch.Tensor:
+        """the same walks from one sharded :meth:`sample_neighbor` (count 1) per hop: the
+        CPU path, and the torch composition the fused hop kernels are measured against.  On
+        the GPU every hop draws from its own Philox stream (``sample_neighbor`` numbers its
+        draws by exchange slot, the same numbers every hop)."""
+        cur = starts.reshape(-1).long()
+        cols = [cur]
+        for s in range(int(walk_len)):
+            sid = int(stream_id) if cur.device.type == "cpu" else (128 + 8 * s + int(stream_id)) % 256
+            nb = self.sample_neighbor(cur, 1, edge_types, -1, sid).reshape(-1).long()
+            cur = torch.where(nb >= 0, nb, torch.full_like(nb, int(default)))
+            cols.append(cur)
+        return torch.stack(cols, 1).int()
 
     # ------------------------------------------------------------------ full neighbourhoods
     def _masked_degree(self, local_rows: torch.Tensor, mask: int) -> torch.Tensor:

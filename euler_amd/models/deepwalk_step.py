@@ -137,11 +137,37 @@ class DeepWalkTrainer:
     def step(self):
         self.steps_done += 1
         if self.static and self.overflow_check_every > 0 and self.steps_done % self.overflow_check_every == 0:
-            self.table.check_overflow()
+            self.check_overflow()
         if self.hip_graph is not None:
             self.hip_graph.replay()
             return self.loss
         return self._step_static() if self.static else self._step_dynamic()
+
+    def check_overflow(self):
+        """host read of the fixed-capacity exchanges' overflow flags (a sync).  On a
+        row-sharded graph the table's flag and the graph's (walk / root exchanges, feature
+        and label exchanges) are MAX-all-reduced over the group first, so every rank raises
+        in the same step: a rank that raised alone would leave its peers waiting in the
+        next step's collective."""
+        g = self.graph
+        if getattr(g, "overflow", None) is None:
+            return self.table.check_overflow()
+        names, words = ["table", "graph"], [self.table.overflow, g.overflow]
+        for name in ("features", "labels"):
+            o = getattr(getattr(g, name, None), "overflow", None)
+            if o is not None:
+                names.append(name)
+                words.append(o)
+        flags = torch.cat([w.reshape(-1)[:1].to(torch.int32) for w in words])
+        if getattr(g, "comm", False):
+            from euler_amd.parallel import comm
+
+            comm.all_reduce(flags, torch.distributed.ReduceOp.MAX, group=g.group)
+        hit = [n for n, f in zip(names, flags.tolist()) if f]
+        if hit:
+            raise RuntimeError("DeepWalkTrainer: the " + ", ".join(hit) + " exchange overflowed its per-peer slots "
+                               "on some rank (those ids were dropped / those walkers ended); raise the capacity "
+                               "(capacity_sigmas)")
 
     def capture(self, warm=2):
         """Record one static step into a hipGraph (after ``warm`` real eager steps on a side
@@ -427,6 +453,14 @@ class DeepWalkEstimatorTrainer:
                 raise ValueError("graph node ids beyond the model's max_id")
             if not np.array_equal(ids, np.arange(ids.size)):
                 row_map = np.concatenate([ids, [self.num - 1]])
+        elif getattr(graph, "row_ids", None) is not None:
+            # a graph built from per-rank engine shards: rows are not in id order; row_ids
+            # (on the device) is every row's node id, -1 for a shard's padding rows
+            rid = graph.row_ids.to(self.device).long()
+            if rid.numel() and int(rid.max().item()) > model.max_id:
+                raise ValueError("graph node ids beyond the model's max_id")
+            pad_row = torch.full((1,), self.num - 1, dtype=torch.int64, device=self.device)
+            row_map = torch.cat([torch.where(rid >= 0, rid, pad_row), pad_row])
         elif graph.num_rows > self.num - 1:
             raise ValueError("graph rows beyond the model's max_id")
         # LINE (second order, examples/line/line.py:27-71): the positive of a root is one
@@ -564,8 +598,18 @@ class DeepWalkEstimatorTrainer:
                                                                          device=self.device)])
         return loss
 
+    def _overflow_due(self, n=1):
+        """on a row-sharded graph: read the exchanges' overflow flags (agreed over the
+        ranks, DeepWalkTrainer.check_overflow) whenever the step count passes a multiple of
+        ``overflow_check_every``"""
+        every = self.inner.overflow_check_every
+        if every > 0 and getattr(self.graph, "overflow", None) is not None and \
+                self.step_count // every != (self.step_count - int(n)) // every:
+            self.inner.check_overflow()
+
     def step(self, grad_sync=None):
         self.step_count += 1
+        self._overflow_due()
         if self._graph_exec is not None:
             self._graph_exec.replay()
             self._loss = self._graph_loss[1]
@@ -600,6 +644,7 @@ class DeepWalkEstimatorTrainer:
             self._graph_exec.replay()
         self._loss = self._graph_loss[1]
         self.step_count += int(n)
+        self._overflow_due(n)
 
     def replay_steps(self, n):
         left = int(n)
@@ -609,6 +654,7 @@ class DeepWalkEstimatorTrainer:
                 self._loss = self._graph_loss[k]
                 left -= k
         self.step_count += int(n)
+        self._overflow_due(n)
 
     def release_graphs(self):
         for g in self._graphs.values():

@@ -779,6 +779,42 @@ def route_by_owner(ids, W: int, C: int, overflow, self_rank: int = -1):
     return pos, send
 
 
+def walk_key_space(num_rows: int, W: int, n: int) -> int:
+    """``R`` of the sharded walk's packed requests ``key = ticket * R + row``: ``num_rows``
+    rounded up to a multiple of ``W`` (so ``key % W == row % W``: ``route_by_owner`` routes
+    the key as it is).  ``W * n`` tickets (every rank walks ``n`` rows) times ``R`` must fit
+    62 bits."""
+    R = max(-(-int(num_rows) // int(W)) * int(W), int(W))
+    if int(W) * int(n) * R >= 1 << 62:
+        raise ValueError(f"sharded walk: {W} ranks x {n} walkers x {R} rows do not fit a 62-bit request key")
+    return R
+
+
+def walk_keys(starts, out, num_rows: int, R: int, W: int, ticket0: int):
+    """hop 0 of a sharded walk (csrc/hip/walk_shard.hip): writes column 0 of ``out
+    [n, walk_len + 1]`` (int32) and returns the request keys ``[n]`` int64,
+    ``(ticket0 + i) * R + starts[i]`` or -1 for a start outside ``[0, num_rows)``"""
+    return hip().walk_keys(starts.contiguous(), out, int(num_rows), int(R), int(W), int(ticket0))
+
+
+def walk_step_owner(req, R: int, W: int, graph, mask: int, hop: int, stream_id: int):
+    """the owner's draw for every received request key ``[m]`` from its local
+    :class:`DeviceGraph` ``graph``: the next global row (int32; -1 for an empty slot or a
+    row with no edge under ``mask``), drawn as ``random_walk_kernel`` draws it with Philox
+    counter ``ticket * 1024 + hop``"""
+    return hip().walk_step_owner(req.contiguous(), int(R), int(W), graph.indptr, graph.nbr, graph.cumw,
+                                 int(graph.num_rows), int(graph.num_types), int(mask) & 0xFFFFFFFF, int(hop),
+                                 graph.rng, int(stream_id))
+
+
+def walk_unroute(back, pos, out, col: int, default: int, num_rows: int, R: int, W: int, ticket0: int):
+    """the returned answers ``back [W*C]`` in walker order: column ``col`` of ``out`` is
+    ``back[pos[i]]``, or ``default`` for the trash slot or a -1 answer; returns the next
+    hop's request keys ``[n]``"""
+    return hip().walk_unroute(back.contiguous(), pos, out, int(col), int(default), int(num_rows), int(R), int(W),
+                              int(ticket0))
+
+
 def occ_csr(inv, n_u):
     """occurrence lists of ``inv`` (values in [0, n_u)): ``(ptr [n_u+1] int64, list int32)``."""
     inv = inv.reshape(-1).long()

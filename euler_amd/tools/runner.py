@@ -224,7 +224,8 @@ def parse_args(argv=None, model=None):
     p.add_argument("--device_graph_sharded", action="store_true",
                    help="with --device_graph: row-shard the graph (CSR, features, labels) over the ranks, "
                         "neighbour draws and features over all-to-all (graph/sharded_graph.py; supervised "
-                        "SageDataFlow models)")
+                        "SageDataFlow / GCNDataFlow models, unsupervised GraphSAGE, and DeepWalk / Node2Vec "
+                        "(p = q = 1) / second-order LINE with their walks answered by the rows' owners)")
     p.add_argument("--engine_shards", action="store_true",
                    help="with --device_graph_sharded: every rank's engine loads only its partitions "
                         "(shard_idx = rank): host memory per rank is 1/W of the graph (training only: "
