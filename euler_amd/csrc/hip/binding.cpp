@@ -602,8 +602,11 @@ void register_graph_cls_ops(pybind11::module& m);
 void register_node_embed_ops(pybind11::module& m);
 // binding_walk_shard.cpp: the hop kernels of random walks over the row-sharded graph
 void register_walk_shard_ops(pybind11::module& m);
+// binding_knn.cpp: fused distance + top-k search (flat and IVF)
+void register_knn_ops(pybind11::module& m);
 
 PYBIND11_MODULE(_hip_ops, m) {
+  register_knn_ops(m);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

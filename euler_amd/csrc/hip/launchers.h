@@ -218,6 +218,21 @@ hipError_t eh_flat_optim2(float* p, const float* g, float* m, float* v, int64_t 
 hipError_t eh_sparse_optim(float* table, float* m, float* v, const int64_t* rows, const void* grads, int grads_bf16,
                            int64_t n, int D, int64_t n_rows, int64_t* step, float lr, float b1, float b2, float eps,
                            int kind, hipStream_t s);
+
+// knn.hip (fused distance + top-k search; partials dist [nq, S, k] fp32 / row [nq, S, k] int64,
+// sorted by (score = ||x||^2 - 2 q.x, row), missing entries +inf / -1)
+int eh_knn_max_k();
+int eh_knn_max_splits();
+hipError_t eh_knn_flat_scan(const float* Q, const float* X, const float* xn, int64_t nq, int64_t n, int d, int k,
+                            int S, float* pd, int64_t* pr, hipStream_t s);
+// XS / xn in list order, list_ptr [ncent + 1], row_of [n] original rows (ascending inside a
+// list), probe [nq, nprobe] (-1: none); the partials have S = nprobe
+hipError_t eh_knn_ivf_scan(const float* Q, const float* XS, const float* xn, const int64_t* list_ptr,
+                           const int64_t* row_of, const int64_t* probe, int64_t nq, int64_t n, int64_t ncent,
+                           int nprobe, int d, int k, float* pd, int64_t* pr, hipStream_t s);
+// D [nq, k] = max(score + qn, 0), I [nq, k] rows, merged under the same ordering
+hipError_t eh_knn_merge(const float* pd, const int64_t* pr, const float* qn, int64_t nq, int S, int k, float* D,
+                        int64_t* I, hipStream_t s);
 }
 
 extern "C" {
