@@ -604,9 +604,12 @@ void register_node_embed_ops(pybind11::module& m);
 void register_walk_shard_ops(pybind11::module& m);
 // binding_knn.cpp: fused distance + top-k search (flat and IVF)
 void register_knn_ops(pybind11::module& m);
+// binding_kg_rank.cpp: link-prediction rank counts (fused score + compare + filter scan)
+void register_kg_rank_ops(pybind11::module& m);
 
 PYBIND11_MODULE(_hip_ops, m) {
   register_knn_ops(m);
+  register_kg_rank_ops(m);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

@@ -233,6 +233,19 @@ hipError_t eh_knn_ivf_scan(const float* Q, const float* XS, const float* xn, con
 // D [nq, k] = max(score + qn, 0), I [nq, k] rows, merged under the same ordering
 hipError_t eh_knn_merge(const float* pd, const int64_t* pr, const float* qn, int64_t nq, int S, int k, float* D,
                         int64_t* I, hipStream_t s);
+
+// kg_rank.hip (link-prediction rank counts: every query row against every candidate row, no
+// [B, N] score matrix).  kind 0 = l1, 1 = squared l2 (lower is better), 2 = dot (higher is
+// better).  ts [B] = score of (Q[b], C[true_idx[b]]), NaN for a true_idx outside [0, N).
+int eh_kg_rank_max_splits();
+hipError_t eh_kg_rank_true(const float* Q, const float* C, const int64_t* true_idx, int64_t B, int64_t N, int d,
+                           int kind, float* ts, hipStream_t s);
+// partial counts better / ties [B, S] int64 over S candidate ranges: candidates e != true_idx[b],
+// not in filt_idx[filt_ptr[b] : filt_ptr[b + 1]] (ascending; filt_ptr == nullptr: no filter;
+// nf = entries of filt_idx), that score strictly better than / equal to ts[b]
+hipError_t eh_kg_rank_scan(const float* Q, const float* C, const int64_t* true_idx, const float* ts,
+                           const int64_t* filt_ptr, const int32_t* filt_idx, int64_t nf, int64_t B, int64_t N, int d,
+                           int kind, int S, int64_t* better, int64_t* ties, hipStream_t s);
 }
 
 extern "C" {

@@ -1,12 +1,17 @@
 """Estimators (reference ``euler_estimator/python/*.py``)."""
 from __future__ import annotations
 
+import logging
+import time
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 import euler_amd.ops.graph_api as ge
 from euler_amd.estimator.base import BaseEstimator, id_file_batches, latest_checkpoint
+
+log = logging.getLogger("euler_amd.estimator")
 
 __all__ = ["BaseEstimator", "NodeEstimator", "EdgeEstimator", "GraphEstimator", "GaeEstimator", "SampleEstimator",
            "latest_checkpoint", "id_file_batches"]
@@ -76,6 +81,70 @@ class EdgeEstimator(BaseEstimator):
 
     def infer_input_fn(self):
         return self.get_input_from_id_file()
+
+    def _known_triples(self, num_entities):
+        """the filter of :meth:`rank_evaluate`: every edge of params["rank_filter_edge_types"]
+        (absent / None: every edge of the graph; []: none, i.e. raw ranking)"""
+        from euler_amd.models.kg_eval import KnownTriples
+        from euler_amd.ops import base
+
+        types = self.params.get("rank_filter_edge_types")
+        if types is not None and len(types) == 0:
+            return None
+        eng = base.get_engine()
+        ids = [-1] if types is None else [int(np.asarray(ge.get_edge_type_id(t)).reshape(-1)[0]) for t in types]
+        src, dst, rel = [], [], []
+        for et in ids:
+            s, d, _, feat = eng.export_edges(et, "dense_id", 1)
+            src.append(np.asarray(s).astype(np.int64))
+            dst.append(np.asarray(d).astype(np.int64))
+            rel.append(np.asarray(feat).reshape(-1).astype(np.int64))
+        return KnownTriples(np.concatenate(src), np.concatenate(rel), np.concatenate(dst), num_entities,
+                            device=self.device)
+
+    @torch.no_grad()
+    def rank_evaluate(self):
+        """Link prediction over the id file's triples ("src dst type" lines, relation = the
+        edge feature ``id``): every true head and tail ranked against all entities
+        (models/kg_eval.py), filtered by the known triples of
+        params["rank_filter_edge_types"].  Returns ``link_prediction``'s dict (mrr / mr /
+        hit@k over both sides, per side under "head" / "tail", and n).  Other params:
+        ``rank_ties`` (pessimistic | optimistic | mean), ``rank_batch``, ``rank_ks``.  With
+        several ranks each one ranks its share of the id file and the sums are all-reduced
+        before the division.  :meth:`evaluate` keeps returning the training metric."""
+        from euler_amd.models import kg_eval
+        from euler_amd.parallel import dp
+
+        self.model.to(self.device)
+        self.model.eval()
+        self.restore(strict=False)
+        batches = [b for b in self.get_input_from_id_file()]
+        triples = torch.cat(batches, 0) if batches else torch.zeros(0, 3, dtype=torch.int64)
+        src, dst = triples[:, 0], triples[:, 1]
+        rel = torch.zeros(0, dtype=torch.int64)
+        if triples.shape[0]:
+            rel = torch.as_tensor(ge.get_edge_dense_feature(triples, ["id"], [1])[0]).reshape(-1).long()
+        known = self._known_triples(int(self.model.node_max_id) + 1)
+        ks = tuple(int(k) for k in self.params.get("rank_ks", (1, 3, 10)))
+        t0 = time.time()
+        ranks = kg_eval.rank_triples(self.model, src, rel, dst, known=known,
+                                     ties=self.params.get("rank_ties", "pessimistic"),
+                                     batch=int(self.params.get("rank_batch", 4096)))
+        sums = torch.stack([kg_eval.rank_sums(ranks[s], ks) for s in ("head", "tail")])
+        if dp.is_distributed():
+            import torch.distributed as dist
+
+            sums = sums if dist.get_backend() == "nccl" else sums.cpu()
+            dist.all_reduce(sums)
+        res = kg_eval.metrics_from_sums(sums.sum(0), ks)
+        res["head"] = kg_eval.metrics_from_sums(sums[0], ks)
+        res["tail"] = kg_eval.metrics_from_sums(sums[1], ks)
+        res["n"] = int(sums[0, -1])
+        if self.rank == 0:
+            log.info("rank_evaluate (%s, %d triples, %.2f s): %s", "raw" if known is None else
+                     "filtered by %d known triples" % len(known), res["n"], time.time() - t0,
+                     {k: v for k, v in res.items() if not isinstance(v, dict)})
+        return res
 
 
 class GraphEstimator(BaseEstimator):

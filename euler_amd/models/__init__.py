@@ -6,7 +6,8 @@
   AdaptiveGCN, AGNN, APPNP, ARMA, DNA, SGCN, TAGCN, GeniePath, LGCN;
 * :mod:`~euler_amd.models.unsupervised` — GraphSAGE-unsup, DeepWalk / Node2Vec, LINE,
   DGI, GAE, VGAE, RGCN;
-* :mod:`~euler_amd.models.knowledge_graph` — TransE, TransH, TransR, TransD, DistMult;
+* :mod:`~euler_amd.models.knowledge_graph` — TransE, TransH, TransR, TransD, DistMult
+  (:mod:`~euler_amd.models.kg_eval`: their filtered link-prediction ranks and metrics);
 * :mod:`~euler_amd.models.graph_classification` — GIN, GatedGraph, GraphGCN, Set2Set;
 """
 from euler_amd.models.graph_classification import GIN, GatedGraph, GraphGCN, Set2SetModel  # noqa: F401

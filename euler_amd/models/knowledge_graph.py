@@ -113,6 +113,50 @@ class TransX(nn.Module):
     def generate_embedding(self, src, dst, neg, rel, rows=None):
         raise NotImplementedError
 
+    # ------------------------------------------------------------------ link-prediction ranking
+    # Hooks of models/kg_eval.py.  Every model's score factors into a per-relation projection
+    # of the entity table (entity_space), a relation vector (relation_row) and a translation
+    # distance or a product (rank_kind) between a query row (rank_query) and a candidate row.
+    relation_dependent = False  # True: entity_space differs per relation
+
+    @property
+    def rank_kind(self):
+        """score kind of ops/kg_rank_ops.rank_counts for this model"""
+        return "l1" if self.l1 else "l2"
+
+    def _rank_table(self, name="entity_encoder"):
+        """rows 0..node_max_id of an entity table (its extra padding row is not a candidate)"""
+        table = getattr(self, name)
+        if isinstance(table, ShardedEmbedding):
+            raise ValueError("link-prediction ranking over a row-sharded entity table (sharded=True) is not "
+                             "supported: build the model with sharded=False")
+        return table.weight[: self.node_max_id + 1]
+
+    def _rank_rel(self, table, rel_id):
+        """row(s) of a relation table: [D] for an int, [n, D] for a tensor of ids"""
+        if isinstance(rel_id, torch.Tensor):
+            return table.weight[table._rows(rel_id.reshape(-1))]
+        return table.weight[int(table._rows(torch.as_tensor([int(rel_id)]))[0])]
+
+    def entity_space(self, rel_id=None):
+        """[node_max_id + 1, D'] candidate rows for relation ``rel_id`` (ignored unless
+        ``relation_dependent``), by the class's own norm_emb / projection"""
+        raise NotImplementedError
+
+    def relation_row(self, rel_id):
+        """the relation vector(s) rho: [D'] for an int id, [n, D'] for a tensor of ids"""
+        return self.norm_emb(self._rank_rel(self.relation_encoder, rel_id))
+
+    def rank_query(self, rows, rho, side):
+        """query rows against entity_space: ``rows`` are the known entities' rows of it (the
+        heads for side "tail", the tails for side "head").  |h + rho - e| = |e - (h + rho)| and
+        |e + rho - t| = |e - (t - rho)|."""
+        if side == "tail":
+            return rows + rho
+        if side == "head":
+            return rows - rho
+        raise ValueError("side must be 'head' or 'tail', got %r" % (side,))
+
     def _lookup(self, name, rows=None):
         """the id -> row function of table ``name``: the module itself, or — in a row-sparse
         step (``rows[name]``: the step's gathered rows) — a gather at the positions the
@@ -167,6 +211,9 @@ class TransE(TransX):
         return (self.norm_emb(e(src)), self.norm_emb(e(dst)), self.norm_emb(e(neg)),
                 self.norm_emb(self.relation_encoder(rel)))
 
+    def entity_space(self, rel_id=None):
+        return self.norm_emb(self._rank_table())
+
 
 class TransH(TransE):
     def __init__(self, *args, **kwargs):
@@ -183,6 +230,11 @@ class TransH(TransE):
         hyper = self.hyper_vector(rel)  # [B, 1, D] broadcasts over negatives
         return (self.projection(e(src), hyper), self.projection(e(dst), hyper), self.projection(e(neg), hyper),
                 self.norm_emb(self.relation_encoder(rel)))
+
+    relation_dependent = True
+
+    def entity_space(self, rel_id=None):
+        return self.projection(self._rank_table(), self._rank_rel(self.hyper_vector, int(rel_id)))
 
 
 class TransR(TransX):
@@ -203,6 +255,12 @@ class TransR(TransX):
         return (self.projection(e(src), mat), self.projection(e(dst), mat), self.projection(e(neg), mat),
                 self.norm_emb(self.relation_encoder(rel)))
 
+    relation_dependent = True
+
+    def entity_space(self, rel_id=None):
+        mat = self._rank_rel(self.transfer_matrix, int(rel_id)).reshape(1, self.ent_dim, self.rel_dim)
+        return self.projection(self._rank_table().unsqueeze(0), mat).squeeze(0)
+
 
 class TransD(TransE):
     def __init__(self, *args, **kwargs):
@@ -219,6 +277,12 @@ class TransD(TransE):
         rt = self.relation_transfer(rel)
         return (self.projection(e(src), et(src), rt), self.projection(e(dst), et(dst), rt),
                 self.projection(e(neg), et(neg), rt), self.norm_emb(self.relation_encoder(rel)))
+
+    relation_dependent = True
+
+    def entity_space(self, rel_id=None):
+        return self.projection(self._rank_table(), self._rank_table("entity_transfer"),
+                               self._rank_rel(self.relation_transfer, int(rel_id)))
 
 
 class DistMult(TransX):
@@ -245,3 +309,14 @@ class DistMult(TransX):
         e = self._lookup("entity_encoder", rows)
         return (self.norm_emb(e(src)), self.norm_emb(e(dst)), self.norm_emb(e(neg)),
                 self.norm_emb(self.relation_encoder(rel)))
+
+    rank_kind = "dot"
+
+    def entity_space(self, rel_id=None):
+        return self.norm_emb(self._rank_table())
+
+    def rank_query(self, rows, rho, side):
+        """sum(h * rho * e) = (h * rho) . e and sum(e * rho * t) = (rho * t) . e"""
+        if side not in ("head", "tail"):
+            raise ValueError("side must be 'head' or 'tail', got %r" % (side,))
+        return rows * rho

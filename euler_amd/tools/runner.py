@@ -8,7 +8,9 @@ id_file, infer_dir, optimizer, learning_rate, run_mode``); ``total_step`` defaul
 ``num_epochs * total_size / batch_size`` like the reference runners.  Data parallelism:
 ``--gpus N`` starts N ranks on this node (parallel/launch.py maybe_spawn), or launch under
 torchrun (``WORLD_SIZE`` > 1 initialises RCCL/gloo automatically); reference launcher
-``tf_euler/scripts/dist_tf_euler.sh:1-49``.
+``tf_euler/scripts/dist_tf_euler.sh:1-49``.  KG models (transe / transh / transr / transd / distmult):
+``--run_mode rank_evaluate`` ranks every test triple's head and tail against all entities
+(``--rank_filter filtered|raw``, ``--rank_ties pessimistic|optimistic|mean``; models/kg_eval.py).
 """
 from __future__ import annotations
 
@@ -199,7 +201,13 @@ def parse_args(argv=None, model=None):
     p.add_argument("--id_file", default=None)
     p.add_argument("--optimizer", default="adam")
     p.add_argument("--learning_rate", type=float, default=0.01)
-    p.add_argument("--run_mode", default="train", choices=["train", "evaluate", "infer", "train_and_evaluate"])
+    p.add_argument("--run_mode", default="train", choices=["train", "evaluate", "infer", "train_and_evaluate",
+                                                              "rank_evaluate"])
+    p.add_argument("--rank_filter", default="filtered", choices=["filtered", "raw"],
+                   help="rank_evaluate: take the other known true answers (every split's triples) out of the "
+                        "candidates, or rank against all entities as they are")
+    p.add_argument("--rank_ties", default="pessimistic", choices=["pessimistic", "optimistic", "mean"],
+                   help="rank_evaluate: where candidates that score exactly like the true entity count")
     p.add_argument("--num_negs", type=int, default=5)
     p.add_argument("--walk_len", type=int, default=3)
     p.add_argument("--walk_p", type=float, default=1.0)
@@ -289,7 +297,8 @@ def build(a):
         est = NodeEstimator(model, params)
     elif kind == "edge":
         params.update(train_edge_type=_first(ds.train_edge_type), id_file=a.id_file or ds.edge_id_file,
-                      infer_type=a.infer_type)
+                      infer_type=a.infer_type, rank_ties=a.rank_ties,
+                      rank_filter_edge_types=list(ds.all_edge_type) if a.rank_filter == "filtered" else [])
         est = EdgeEstimator(model, params)
     else:
         params.update(label=[ds.label_idx], num_classes=ds.num_classes, id_file=a.id_file or ds.id_file)
@@ -313,6 +322,10 @@ def main(argv=None, model=None):
         return est.evaluate()
     if a.run_mode == "infer":
         return est.infer()
+    if a.run_mode == "rank_evaluate":
+        if not callable(getattr(est, "rank_evaluate", None)):
+            raise SystemExit("--run_mode rank_evaluate is for the knowledge-graph models")
+        return est.rank_evaluate()
     return est.train_and_evaluate()
 
 
