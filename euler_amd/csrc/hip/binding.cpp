@@ -606,10 +606,13 @@ void register_walk_shard_ops(pybind11::module& m);
 void register_knn_ops(pybind11::module& m);
 // binding_kg_rank.cpp: link-prediction rank counts (fused score + compare + filter scan)
 void register_kg_rank_ops(pybind11::module& m);
+// binding_sage_csr.cpp: full-neighbourhood GraphSAGE layer over the graph's CSR (layer-wise inference)
+void register_sage_csr_ops(pybind11::module& m);
 
 PYBIND11_MODULE(_hip_ops, m) {
   register_knn_ops(m);
   register_kg_rank_ops(m);
+  register_sage_csr_ops(m);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

@@ -234,6 +234,17 @@ hipError_t eh_knn_ivf_scan(const float* Q, const float* XS, const float* xn, con
 hipError_t eh_knn_merge(const float* pd, const int64_t* pr, const float* qn, int64_t nq, int S, int k, float* D,
                         int64_t* I, hipStream_t s);
 
+// sage_csr.hip (full-neighbourhood GraphSAGE layer over the graph's own CSR: weight-normalised
+// mean of x over the masked (row, type) segments, then act([x_self | ns * mean + ss * x_self] @ W^T)).
+// x [N, Dp] bf16 / fp32 (Dp % 16 == 0, <= 512), W [Hp, 2 Dp] bf16 row-major (Hp % 64 == 0),
+// rows [M] int32 or nullptr (= rows 0 .. M - 1), out [M, Hp] bf16 / fp32.  A rows entry or a
+// neighbour outside [0, N) reads nothing: a zero output row / a zero contribution.
+int eh_sage_csr_hub_degree();
+hipError_t eh_sage_csr_fwd(const int64_t* indptr, const int32_t* nbr, const float* cumw, int64_t N, int64_t E, int T,
+                           uint32_t mask, const void* x, int x_fp32, int Dp, const int32_t* rows, int64_t M,
+                           const void* W, int Hp, float nbr_scale, float self_scale, int relu, void* out,
+                           int out_fp32, hipStream_t s);
+
 // kg_rank.hip (link-prediction rank counts: every query row against every candidate row, no
 // [B, N] score matrix).  kind 0 = l1, 1 = squared l2 (lower is better), 2 = dot (higher is
 // better).  ts [B] = score of (Q[b], C[true_idx[b]]), NaN for a true_idx outside [0, N).

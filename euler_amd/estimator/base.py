@@ -871,6 +871,32 @@ class BaseEstimator:
             else:
                 yield None, {"pad_to": pad}
 
+    def _infer_mode(self) -> str:
+        """``params["infer_mode"]``: "sampled" (default: a fresh sampled tree per root) or
+        "layerwise" (deterministic full-neighbourhood inference, models/sage_infer.py)"""
+        mode = self.params.get("infer_mode") or "sampled"
+        if mode not in ("sampled", "layerwise"):
+            raise ValueError(f"infer_mode must be 'sampled' or 'layerwise', got {mode!r}")
+        return mode
+
+    def _layerwise_trainer(self):
+        """the device trainer of ``infer_mode="layerwise"``; never a fallback: a ValueError
+        names why this estimator has none"""
+        if not self.params.get("device_graph"):
+            raise ValueError("infer_mode='layerwise' runs on the HBM graph: set device_graph=True")
+        if self.params.get("device_infer", True) is False:
+            raise ValueError("infer_mode='layerwise' is device inference: device_infer=False turns it off")
+        tr = self._device_inference_trainer()
+        if tr is None:
+            raise ValueError(f"infer_mode='layerwise': {type(self.model).__name__} has no device inference trainer "
+                             "(layer-wise inference covers SupervisedGraphSage on an unsharded device graph)")
+        if not callable(getattr(tr, "infer_logits_layerwise", None)) or \
+                not callable(getattr(tr, "infer_embed_layerwise", None)):
+            raise ValueError(f"infer_mode='layerwise': {type(tr).__name__} has no layer-wise inference (it covers "
+                             "SageTrainer on an unsharded device graph; sharded, GCN-family and unsupervised "
+                             "trainers infer with infer_mode='sampled')")
+        return tr
+
     def _device_evaluate(self, tr):
         """loss and the model's streaming metric over the eval id batches, every batch's
         block / tree built and run on the device"""
@@ -882,12 +908,13 @@ class BaseEstimator:
         name = getattr(self.model, "metric_name", getattr(tr, "metric_name", "f1"))
         losses, res, steps, n, t0 = [], {}, 0, 0, time.time()
         extract = lambda b: self.get_evaluate_from_input(b, self.params)  # noqa: E731
+        infer_logits = tr.infer_logits_layerwise if self._infer_mode() == "layerwise" else tr.infer_logits
         for src, kw in self._lockstep_batches(tr, self._eval_batches(), extract, self.evaluate_stop_onetime):
             if src is None:  # a padding batch of the collective loop
                 tr.infer_logits(torch.zeros(0, dtype=torch.int64), **kw)
                 continue
             try:
-                _, logits, y = tr.infer_logits(src, **kw)
+                _, logits, y = infer_logits(src, **kw)
             except NotImplementedError:
                 return None
             losses.append(float(F.binary_cross_entropy_with_logits(logits, y.float())))
@@ -906,12 +933,13 @@ class BaseEstimator:
         ids_out, emb_out = [], []
         n, t0 = 0, time.time()
         extract = lambda b: self.get_infer_from_input(b, self.params)  # noqa: E731
+        infer_embed = tr.infer_embed_layerwise if self._infer_mode() == "layerwise" else tr.infer_embed
         for src, kw in self._lockstep_batches(tr, self.infer_input_fn(), extract):
             if src is None:  # a padding batch of the collective loop
                 tr.infer_embed(torch.zeros(0, dtype=torch.int64), **kw)
                 continue
             try:
-                emb = tr.infer_embed(src, **kw)
+                emb = infer_embed(src, **kw)
             except NotImplementedError:
                 return None
             s, e = self.transfer_embedding(src, emb)
@@ -934,7 +962,7 @@ class BaseEstimator:
 
     @torch.no_grad()
     def evaluate(self):
-        tr = self._device_inference_trainer()
+        tr = self._layerwise_trainer() if self._infer_mode() == "layerwise" else self._device_inference_trainer()
         if tr is not None and callable(getattr(tr, "infer_logits", None)):
             res = self._device_evaluate(tr)
             if res is not None:
@@ -971,7 +999,7 @@ class BaseEstimator:
 
     @torch.no_grad()
     def infer(self):
-        tr = self._device_inference_trainer()
+        tr = self._layerwise_trainer() if self._infer_mode() == "layerwise" else self._device_inference_trainer()
         if tr is not None and callable(getattr(tr, "infer_embed", None)):
             out = self._device_infer(tr)
             if out is not None:

@@ -383,6 +383,7 @@ class SageTrainer:
             self._pack({k: torch.as_tensor(v) for k, v in logical.items()}, self.flat)
             self.refresh_shadows()
         else:
+            self._param_version = getattr(self, "_param_version", 0) + 1
             with torch.no_grad():
                 for k, v in logical.items():
                     self._cpu_params[k].copy_(torch.as_tensor(v).to(self._cpu_params[k]))
@@ -390,6 +391,7 @@ class SageTrainer:
     def refresh_shadows(self):
         """Rebuild the bf16 weight shadows from the fp32 parameters (after an external
         write such as a load or the data-parallel broadcast)."""
+        self._param_version = getattr(self, "_param_version", 0) + 1  # drops cached layer-wise tables
         if self.on_gpu:
             self.plan.opt(3)
 
@@ -469,6 +471,7 @@ class SageTrainer:
         p.opt(0)
 
     def optimizer_step(self, grad_scale: float = 1.0):
+        self._param_version = getattr(self, "_param_version", 0) + 1
         self.plan.opt(1, float(grad_scale))
 
     def grad_buckets(self):
@@ -747,6 +750,66 @@ class SageTrainer:
 
     def infer_embed(self, ids):
         return self.infer_logits(ids)[0]
+
+    # ------------------------------------------------------------------ layer-wise inference
+    def _unfm(self, sh, rows, cols):
+        """row-major [rows, cols] view of a fragment-major bf16 weight shadow (csrc/hip/tile.h
+        fm_off: [rows / 16][cols / 32][4 k-groups][16 rows][8 k])"""
+        return sh.view(rows // 16, cols // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(rows, cols)
+
+    def _layerwise_weights(self):
+        """(conv weights, fc, out_fc) for models/sage_infer.py: the bf16 weight shadows of the
+        training kernels on the GPU (padded layout), the logical fp32 parameters on a CPU"""
+        L = self.L
+        if self.on_gpu:
+            b = self._buf
+            hin = [self.Dp] + self.Hp[:-1]
+            convs = [self._unfm(b[f"W{k}_sh"], self.Hp[k], 2 * hin[k]) for k in range(L)]
+            fc = (self._unfm(b["Wfc_sh"], self.Ep, self.Hp[-1]), b["bfc"])
+            return convs, fc, self._unfm(b["Wout_sh"], self.Cp, self.Ep)
+        P = {k: v.detach().float() for k, v in self._cpu_params.items()}
+        convs = []
+        for k in range(L):
+            ws, wn = P[f"gnn.convs.{k}.self_fc.weight"], P[f"gnn.convs.{k}.neigh_fc.weight"]
+            if k == 0 and self.Dp != self.D:  # the feature table is padded to Dp columns
+                pad = torch.zeros(ws.shape[0], self.Dp - self.D)
+                ws, wn = torch.cat([ws, pad], 1), torch.cat([wn, pad], 1)
+            convs.append(torch.cat([ws, wn], 1))
+        return convs, (P["gnn.fc.weight"], P["gnn.fc.bias"]), P["out_fc.weight"]
+
+    def layerwise(self):
+        """the :class:`LayerwiseSageInference` of this trainer's current parameters; its cached
+        hidden table lives until the parameters change (a step, a load)"""
+        from euler_amd.models.sage_infer import LayerwiseSageInference
+
+        if self.fshard is not None:
+            raise ValueError("layer-wise inference reads a whole feature table: row-sharded features have none")
+        key = (self.step_count, getattr(self, "_param_version", 0))
+        lw = getattr(self, "_lw", None)
+        if lw is None or self._lw_key != key:
+            convs, fc, out_fc = self._layerwise_weights()
+            if lw is None:
+                feats = self.features if self.on_gpu else self.features.float()
+                lw = self._lw = LayerwiseSageInference(self.graph, feats, convs, self.fanouts, self.masks,
+                                                       self.include_self, fc=fc, out_fc=out_fc, embed_dim=self.E,
+                                                       logits_dim=self.C)
+            else:
+                lw.set_weights(convs, fc, out_fc)
+            self._lw_key = key
+        return lw
+
+    @torch.no_grad()
+    def infer_logits_layerwise(self, ids):
+        """(embeddings [n, E], logits [n, C], labels [n, C]) of raw node ids by layer-wise
+        full-neighbourhood inference (models/sage_infer.py): deterministic, every layer the
+        expected aggregator of the sampled path.  Same tuple and id handling as
+        :meth:`infer_logits`."""
+        rows = self.graph.rows_of(ids).to(self.graph.device)
+        emb, logits = self.layerwise().logits(rows.clamp(min=0))
+        return emb, logits, self._labels_of(rows.clamp(min=0)).to(emb.device)
+
+    def infer_embed_layerwise(self, ids):
+        return self.infer_logits_layerwise(ids)[0]
 
     def logical_forward(self, params, roots, nodes, leaf, table=None):
         """fp32 logits of the model for one sampled slotted tree (``table``: the feature rows

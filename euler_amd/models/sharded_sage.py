@@ -37,6 +37,10 @@ class ShardedSageTrainer(SageTrainer):
     # evaluate / infer on the device, collectively: every rank calls with batches of the same
     # padded size in lockstep (estimator/base.py _lockstep_batches)
     collective_infer = True
+    # layer-wise inference walks one whole CSR and feature table: a row-sharded graph has
+    # neither (estimator infer_mode="layerwise" reports that instead of falling back)
+    infer_logits_layerwise = None
+    infer_embed_layerwise = None
 
     def __init__(self, graph, batch_size, fanouts, dims, label_dim, **kw):
         self.sgraph = graph

@@ -239,6 +239,10 @@ def parse_args(argv=None, model=None):
                         "(shard_idx = rank): host memory per rank is 1/W of the graph (training only: "
                         "an engine-path evaluate would see one shard)")
     p.add_argument("--device_feature_dtype", default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--infer_mode", default="sampled", choices=["sampled", "layerwise"],
+                   help="with --device_graph, evaluate / infer: a fresh sampled tree per root (sampled) or "
+                        "deterministic layer-wise full-neighbourhood inference on the fused CSR-mean kernel "
+                        "(layerwise; graphsage: models/sage_infer.py)")
     p.add_argument("--cuda_graph", default="auto", choices=["auto", "off"],
                    help="capture the engine-path training step in a hipGraph when eligible")
     p.add_argument("--native_pipeline", default="auto", choices=["auto", "on", "off"],
@@ -287,7 +291,7 @@ def build(a):
               "device": a.device, "amp": a.amp, "device_graph": a.device_graph or a.device_graph_sharded,
               "device_graph_sharded": ("engine_shards" if a.engine_shards else True) if a.device_graph_sharded
               else False,
-              "device_feature_dtype": a.device_feature_dtype, "seed": a.seed,
+              "device_feature_dtype": a.device_feature_dtype, "infer_mode": a.infer_mode, "seed": a.seed,
               "native_pipeline": {"auto": "auto", "on": True, "off": False}[a.native_pipeline],
               "cuda_graph": a.cuda_graph if a.cuda_graph == "auto" else False,
               "pipeline_workers": a.pipeline_workers,
