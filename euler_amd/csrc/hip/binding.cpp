@@ -608,11 +608,14 @@ void register_knn_ops(pybind11::module& m);
 void register_kg_rank_ops(pybind11::module& m);
 // binding_sage_csr.cpp: full-neighbourhood GraphSAGE layer over the graph's CSR (layer-wise inference)
 void register_sage_csr_ops(pybind11::module& m);
+// binding_graph_build.cpp: edge list -> device CSR (DeviceGraph.from_edges)
+void register_graph_build_ops(pybind11::module& m);
 
 PYBIND11_MODULE(_hip_ops, m) {
   register_knn_ops(m);
   register_kg_rank_ops(m);
   register_sage_csr_ops(m);
+  register_graph_build_ops(m);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

@@ -257,6 +257,33 @@ hipError_t eh_kg_rank_true(const float* Q, const float* C, const int64_t* true_i
 hipError_t eh_kg_rank_scan(const float* Q, const float* C, const int64_t* true_idx, const float* ts,
                            const int64_t* filt_ptr, const int32_t* filt_idx, int64_t nf, int64_t B, int64_t N, int d,
                            int kind, int S, int64_t* better, int64_t* ties, hipStream_t s);
+
+// graph_build.hip (DeviceGraph.from_edges: edge list -> per-(row, type) CSR).  Keys are
+// ((row * T + type) << dst_bits) | dst_row, at most 63 bits; payloads are edge indices (the
+// reverse copy of edge i under `symmetric` is E + i); status int64 [4]: [0] failure bits
+// (1 id, 2 type, 4 weight), [1] ids out of range, [2] runs of equal keys (eh_gb_heads).
+int eh_gb_short_len();  // longest segment the prefix kernel sums with one lane
+int eh_gb_wave_len();   // longest segment it sums with one wave (longer: one block)
+// src / dst int32 or int64 [E]; w (null: 1), et (null: 0), ids (null: an id is its row) sorted
+// unique as unsigned 64-bit [N]; keys / idx [E] ([2 E] with symmetric)
+hipError_t eh_gb_pack(const void* src, int src64, const void* dst, int dst64, const float* w, const int32_t* et,
+                      const int64_t* ids, int64_t N, int T, int dst_bits, int64_t E, int symmetric, int64_t* keys,
+                      int32_t* idx, int64_t* status, hipStream_t s);
+// stable; (keys_a, idx_a) hold the input, both pairs are the sort's ping-pong buffers and
+// *result_in_b says which pair holds the output; temp null: *temp_bytes receives the scratch
+// size and nothing runs
+hipError_t eh_gb_sort(int64_t* keys_a, int64_t* keys_b, int32_t* idx_a, int32_t* idx_b, int64_t n, int end_bit,
+                      void* temp, size_t* temp_bytes, int* result_in_b, hipStream_t s);
+// incl [n]: inclusive count of run heads of the sorted keys (head [n]: scratch)
+hipError_t eh_gb_heads(const int64_t* keys, int64_t n, int32_t* head, int32_t* incl, int64_t* status, void* temp,
+                       size_t* temp_bytes, hipStream_t s);
+// one entry per run: its key, its first payload, the fp64 sum of its weights in input order
+hipError_t eh_gb_compact(const int64_t* keys, const int32_t* idx, const int32_t* incl, int64_t n, const float* w,
+                         int64_t E, int64_t nnz, int64_t* ckeys, int32_t* cidx, float* cw, hipStream_t s);
+// indptr [N T + 1], nbr / cumw [nnz] of sorted keys; perm (payloads) with w [E] or null, or
+// perm null and w [nnz] the slots' own weights
+hipError_t eh_gb_csr(const int64_t* keys, int64_t nnz, int64_t N, int T, int dst_bits, const float* w,
+                     const int32_t* perm, int64_t E, int64_t* indptr, int32_t* nbr, float* cumw, hipStream_t s);
 }
 
 extern "C" {

@@ -511,6 +511,17 @@ class BaseEstimator:
 
         return build_device_trainer(self, self.model, first)
 
+    def _first_batch(self):
+        """the engine batch that materialises the model's lazy layers before a device trainer is
+        built; with ``params["device_graph_factory"]`` there is no engine: None, after the lazy
+        layers got their widths from the model's own dims"""
+        if self.params.get("device_graph_factory"):
+            from euler_amd.estimator.device_trainers import materialize_without_engine
+
+            materialize_without_engine(self.model)
+            return None
+        return self.get_train_from_input(self.train_input_fn(), self.params)
+
     def _train_device_graph(self):
         """NodeEstimator.train() on the device path: the whole mini-batch pipeline
         (sample_node roots, SageDataFlow hops, feature / label lookup) and the model step
@@ -529,9 +540,8 @@ class BaseEstimator:
         save_steps = int(self.run_config.get("save_checkpoints_steps", self.params.get("save_checkpoints_steps", 0))
                          or 0)
         # a graph from params["device_graph_factory"] has no engine to draw a first batch from
-        # (it only materialises lazy layers, which such models must not have)
-        first = None if self.params.get("device_graph_factory") else \
-            self.get_train_from_input(self.train_input_fn(), self.params)
+        # (it only materialises lazy layers: those get their widths from the model's own dims)
+        first = self._first_batch()
         self.model.train()
         tr = self._device_graph_trainer(first)
         self.device_trainer = tr
@@ -838,8 +848,7 @@ class BaseEstimator:
             if not device_infers(self.model):
                 return None
             try:
-                first = self.get_train_from_input(self.train_input_fn(), self.params)
-                tr = self._device_graph_trainer(first)
+                tr = self._device_graph_trainer(self._first_batch())
             except (ValueError, NotImplementedError) as e:
                 log.info("no device trainer for %s (%s): engine-path evaluate / infer", type(self.model).__name__, e)
                 return None

@@ -122,6 +122,43 @@ def device_infers(model) -> bool:
     return not isinstance(sampler, (D.FastGCNDataFlow, D.LayerwiseDataFlow))
 
 
+def materialize_without_engine(model):
+    """Lazy layers of a feature-GNN model (``model.gnn``: a conv stack over
+    ``gnn.feature_dim``-wide inputs, ``gnn.fc``, the head's ``out_fc``) materialised without a
+    first engine batch -- a graph from ``params["device_graph_factory"]`` has no engine to draw
+    one from: one no-grad pass of zeros through the dense layers over a two-node block.  A
+    model without lazy layers is left alone; any other model with lazy layers is refused."""
+    import torch.nn.functional as F
+    from torch.nn.parameter import UninitializedParameter
+
+    def lazy():
+        return any(isinstance(p, UninitializedParameter) for p in model.parameters())
+
+    if not lazy():
+        return
+    gnn = getattr(model, "gnn", None)
+    dims = getattr(gnn, "feature_dim", None)
+    if gnn is None or dims is None or not hasattr(gnn, "convs") or not hasattr(gnn, "fc"):
+        raise ValueError(f"device_graph_factory: {type(model).__name__} has lazy layers that only a first engine "
+                         "batch can materialise")
+    width = int(sum(dims)) if isinstance(dims, (list, tuple)) else int(dims)
+    dev = next((p.device for p in model.parameters() if not isinstance(p, UninitializedParameter)),
+               torch.device("cpu"))
+    x = torch.zeros(2, width, device=dev)
+    edge_index = torch.tensor([[0, 1], [0, 1]], dtype=torch.int64, device=dev)
+    was = model.training
+    with torch.no_grad():
+        for conv in gnn.convs:
+            x = F.relu(conv((x, x), edge_index, size=(2, 2)))
+        x = gnn.fc(x)
+        if hasattr(model, "out_fc"):
+            model.out_fc(x)
+    model.train(was)
+    if lazy():
+        raise ValueError(f"device_graph_factory: {type(model).__name__} keeps lazy layers outside its conv stack "
+                         "that only a first engine batch can materialise")
+
+
 def build_device_trainer(est, model, first):
     """the first registered trainer that accepts ``model`` (NoDeviceTrainer if none does).
     A model with a historical-embedding encoder is only taken by a store-aware trainer:

@@ -250,6 +250,109 @@ class DeviceGraph:
         return cls(indptr_t, _upload(nbr, torch.int32, device), cumw, num_types, prob, alias, ids, seed, device)
 
     @classmethod
+    def from_edges(cls, src, dst, weight=None, edge_type=None, *, num_types=None, node_ids=None, num_nodes=None,
+                   symmetric=False, duplicates="keep", node_weights=None, features=None, labels=None,
+                   feature_dtype=torch.bfloat16, seed=0, device="cuda", return_edge_order=False):
+        """From an edge list: ``src`` / ``dst`` int32 or int64 node ids ``[E]`` (tensors or numpy
+        arrays, on the host or already on ``device``), optional fp32 ``weight`` (default 1, must
+        be finite and >= 0) and int ``edge_type`` in ``[0, num_types)`` (default 0; ``num_types``
+        defaults to ``max + 1`` and is at most 32).  The CSR is built on ``device``
+        (``ops/graph_build_ops.py``: gfx950 kernels on a GPU, their torch twin on the CPU) in
+        :meth:`from_csr`'s layout: neighbours ascending inside every (row, type) segment, equal
+        neighbours in input order, fp32 prefix sums accumulated in fp64.
+
+        Rows: with ``num_nodes = N`` and no ``node_ids`` an id is its row (ids outside
+        ``[0, N)`` raise ValueError).  Otherwise the node set is the sorted unique of
+        ``node_ids``, ``src`` and ``dst`` (``node_ids`` adds isolated nodes), ``graph.ids``
+        holds it and :meth:`rows_of` maps ids to rows.
+
+        ``symmetric`` adds the reverse of every edge (same weight and type) before duplicate
+        handling; ``duplicates="keep"`` keeps parallel edges as separate entries, ``"sum"``
+        merges equal (src, type, dst) into one entry with the summed weight.
+
+        ``features`` / ``labels``: ``[len(node_ids), .]`` tables in the order of ``node_ids``
+        (row order when ids are rows), stored as :meth:`from_engine` stores them
+        (``feature_dtype`` / fp32; nodes outside ``node_ids`` get zero rows).  ``node_weights``
+        (same order): the root sampler's weights (:func:`build_alias_table`).
+
+        ``return_edge_order=True``: returns ``(graph, order)``, ``order`` int64 ``[nnz]`` = the
+        input edge behind every CSR slot (``E + i``: the reverse copy of edge ``i``; under
+        ``"sum"`` the first edge of the merged run), e.g. to carry per-edge data along.
+
+        Limits: ``E`` after symmetrisation < 2^31, ``N`` < 2^31, ``num_types`` <= 32."""
+        from euler_amd.ops import graph_build_ops as gb
+
+        device = torch.device(device)
+
+        def ints(a, name):
+            t = torch.as_tensor(a).reshape(-1)
+            if t.dtype == torch.uint64:
+                t = t.view(torch.int64)
+            if t.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"from_edges: {name} must be int32 or int64, got {t.dtype}")
+            return t.to(device)
+
+        src, dst = ints(src, "src"), ints(dst, "dst")
+        E = src.numel()
+        if dst.numel() != E:
+            raise ValueError(f"from_edges: src ({E}) and dst ({dst.numel()}) differ in length")
+        if weight is not None:
+            weight = torch.as_tensor(weight).reshape(-1).to(device=device, dtype=torch.float32)
+            if weight.numel() != E:
+                raise ValueError(f"from_edges: weight ({weight.numel()}) and src ({E}) differ in length")
+        if edge_type is not None:
+            edge_type = torch.as_tensor(edge_type).reshape(-1).to(device=device, dtype=torch.int32)
+            if edge_type.numel() != E:
+                raise ValueError(f"from_edges: edge_type ({edge_type.numel()}) and src ({E}) differ in length")
+        if num_types is None:
+            num_types = int(edge_type.max()) + 1 if edge_type is not None and E else 1
+        T = int(num_types)
+        if not 1 <= T <= gb.MAX_TYPES:
+            raise ValueError(f"from_edges: num_types = {T} is outside [1, {gb.MAX_TYPES}] (edge-type masks are "
+                             "32-bit)")
+        relabel = node_ids is not None or num_nodes is None
+        if relabel:
+            given = None if node_ids is None else ints(node_ids, "node_ids").long()
+            ids_t = gb.unique_ids(([] if given is None else [given]) + [src, dst])
+            N = int(ids_t.numel())
+            if num_nodes is not None and int(num_nodes) != N:
+                raise ValueError(f"from_edges: num_nodes = {num_nodes} but node_ids, src and dst hold {N} ids")
+        else:
+            given, ids_t, N = None, None, int(num_nodes)
+            if N < 0:
+                raise ValueError("from_edges: num_nodes must be >= 0")
+        indptr, nbr, cumw, order = gb.build_csr(src, dst, weight, edge_type, ids_t, num_rows=N, num_types=T,
+                                                symmetric=symmetric, duplicates=duplicates,
+                                                want_order=return_edge_order)
+
+        def to_rows(table, name, dtype):
+            """the [N_input, .] table in row order"""
+            t = torch.as_tensor(table)
+            t = t.reshape(t.shape[0], -1).to(device=device, dtype=torch.float32)
+            n_in = N if given is None else given.numel()
+            if relabel and given is None:
+                raise ValueError(f"from_edges: {name} are in the order of node_ids: pass node_ids (or num_nodes)")
+            if t.shape[0] != n_in:
+                raise ValueError(f"from_edges: {name} has {t.shape[0]} rows for {n_in} nodes")
+            if given is not None:
+                rows, _ = gb.rows_of_ids(given, ids_t)
+                t = torch.zeros((N, t.shape[1]), dtype=torch.float32, device=device).index_copy_(0, rows, t)
+            return t.to(dtype)
+
+        prob = alias = None
+        if node_weights is not None:
+            nw = to_rows(np.asarray(node_weights, np.float32), "node_weights", torch.float32).reshape(-1)
+            prob, alias = build_alias_table(nw.cpu().numpy())
+            prob, alias = torch.from_numpy(prob), torch.from_numpy(alias)
+        ids = None if ids_t is None else ids_t.cpu().numpy().view(np.uint64)
+        g = cls(indptr, nbr, cumw, T, prob, alias, ids, seed, device)
+        if features is not None:
+            g.features = to_rows(features, "features", feature_dtype)
+        if labels is not None:
+            g.labels = to_rows(labels, "labels", torch.float32)
+        return (g, order) if return_edge_order else g
+
+    @classmethod
     def from_engine(cls, engine=None, node_type=-1, features=(), feature_dims=(), label=None, label_dim=None,
                     feature_dtype=torch.bfloat16, seed=0, device="cuda", share=False, sparse_features=()):
         """Upload the engine's local graph shard to HBM.

@@ -121,6 +121,8 @@ def _type_ids(values, table, what):
             if v == "-1":
                 out.append(-1)
                 continue
+            if callable(table):
+                table = table()  # the engine's type names, fetched when a name needs them
             if v not in table:
                 raise ValueError("unknown %s type name %r (known: %s)" % (what, v, sorted(table)))
             out.append(int(table[v]))
@@ -131,11 +133,11 @@ def _type_ids(values, table, what):
 
 def get_node_type_id(type_id_or_names):
     """Names -> ids (ids pass through), reference ``type_ops.get_node_type_id``."""
-    return _t(_type_ids(type_id_or_names, _meta()["node_types"], "node"))
+    return _t(_type_ids(type_id_or_names, lambda: _meta()["node_types"], "node"))
 
 
 def get_edge_type_id(type_id_or_names):
-    return _t(_type_ids(type_id_or_names, _meta()["edge_types"], "edge"))
+    return _t(_type_ids(type_id_or_names, lambda: _meta()["edge_types"], "edge"))
 
 
 def _et(edge_types):
