@@ -1,41 +1,29 @@
 // torch binding of the fused GCN training step (gcn.hip, gcn_args.h).
 //
 // A GcnPlan is built once per trainer (and again when the flow's capacities grow) from a
-// dict of device tensors and sizes; every operand is validated here, the argument blocks
-// are filled once and step() only launches, on torch's current stream: the root draw, three
-// launches per hop, the outer layer (L = 2), the head, d(W0) (L = 2) and the reduce into the
-// flat gradient — hipGraph-capturable (no allocation, no host sync).  The flat optimizer
-// runs after it (parallel/flat.py), with the data-parallel all-reduce in between.
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-
-#include <string>
-#include <vector>
-
+// dict of device tensors and sizes; every operand is validated here (PlanDict,
+// binding_util.h), the argument blocks are filled once and step() only launches, on torch's
+// current stream: the root draw, three launches per hop, the outer layer (L = 2), the head,
+// d(W0) (L = 2) and the reduce into the flat gradient — hipGraph-capturable (no allocation, no
+// host sync).  The flat optimizer runs after it (parallel/flat.py), with the data-parallel
+// all-reduce in between.
+#include "hip/binding_util.h"
 #include "hip/gcn_args.h"
 #include "hip/launchers.h"
 
-namespace py = pybind11;
+using namespace euler_bind;
 using namespace euler_hip;
 
 namespace {
-
-hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
-
-void ok(hipError_t e, const char* what) {
-  TORCH_CHECK(e == hipSuccess, "euler_amd GCN kernel '", what, "' failed: ", hipGetErrorString(e));
-}
 
 int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // LDS / staged image stride of a width (gcn.hip img_ld; kWide = 144 for fc / label widths)
 int64_t img_ld(int64_t w) { return w <= 64 ? 80 : 144; }
 
-class GcnPlan {
+class GcnPlan : private PlanDict {
  public:
-  explicit GcnPlan(py::dict d) : d_(d) {
+  explicit GcnPlan(py::dict d) : PlanDict(d, "GcnPlan") {
     L_ = geti("L");
     B_ = geti("B");
     self_ = static_cast<int32_t>(geti("self_loops"));
@@ -44,7 +32,6 @@ class GcnPlan {
     torch::Tensor indptr = T("indptr"), nbr = T("nbr");
     need(indptr, torch::kInt64, -1, "indptr");
     need(nbr, torch::kInt32, -1, "nbr");
-    dev_ = indptr.device();
     const int64_t types = geti("num_types");
     TORCH_CHECK(types >= 1 && types <= 32 && (indptr.numel() - 1) % types == 0, "GcnPlan: indptr must be [N*T+1]");
     g_.indptr = indptr.data_ptr<int64_t>();
@@ -84,18 +71,18 @@ class GcnPlan {
   // one training step up to the flat gradient (loss_out, counts, overflow updated on the device)
   // fused_opt: the reduce launch also applies the flat optimizer (set_optimizer)
   void step(bool fused_opt) {
-    const c10::DeviceGuard guard(dev_);
+    const c10::DeviceGuard guard(device());
     step_until_head();
-    hipStream_t s = stream();
+    hipStream_t s = cur_stream();
     TORCH_CHECK(!fused_opt || red_opt_.fuse_opt, "GcnPlan: set_optimizer first");
     GcnHeadArgs ha = head_;
     if (fused_opt) ha.ostep_inc = opt_step_;  // the optimizer's step, read by the reduce below
-    ok(eh_gcn_head(&ha, s), "gcn_head");
-    if (L_ == 2) ok(eh_gcn_dw(&dw_, dw_blocks_, s), "gcn_dw");
+    launch_ok(eh_gcn_head(&ha, s), "gcn_head");
+    if (L_ == 2) launch_ok(eh_gcn_dw(&dw_, dw_blocks_, s), "gcn_dw");
     if (fused_opt) {
-      ok(eh_gcn_reduce(&red_opt_, s), "gcn_reduce(opt)");
+      launch_ok(eh_gcn_reduce(&red_opt_, s), "gcn_reduce(opt)");
     } else {
-      ok(eh_gcn_reduce(&red_, s), "gcn_reduce");
+      launch_ok(eh_gcn_reduce(&red_, s), "gcn_reduce");
     }
   }
 
@@ -141,47 +128,47 @@ class GcnPlan {
   }
 
   void step_until_head() {
-    hipStream_t s = stream();
+    hipStream_t s = cur_stream();
     for (int h = 0; h < L_; ++h) {  // hop 0's expand also draws the roots
-      if (hops_[h].lflag) ok(eh_gcn_layer_draw(&draws_[h], s), "gcn_layer_draw");
-      ok(eh_gcn_expand(&hops_[h], s), "gcn_expand");
-      ok(eh_gcn_mark(&hops_[h], s), "gcn_mark");
-      ok(eh_gcn_place(&hops_[h], s), "gcn_place");
+      if (hops_[h].lflag) launch_ok(eh_gcn_layer_draw(&draws_[h], s), "gcn_layer_draw");
+      launch_ok(eh_gcn_expand(&hops_[h], s), "gcn_expand");
+      launch_ok(eh_gcn_mark(&hops_[h], s), "gcn_mark");
+      launch_ok(eh_gcn_place(&hops_[h], s), "gcn_place");
     }
-    if (L_ == 2) ok(eh_gcn_layer(&layer_, s), "gcn_layer");
+    if (L_ == 2) launch_ok(eh_gcn_layer(&layer_, s), "gcn_layer");
   }
 
   // per-phase wall-clock stamps of the head launch (one eager step; diagnostics)
   torch::Tensor head_profile() {
-    const c10::DeviceGuard guard(dev_);
+    const c10::DeviceGuard guard(device());
     const int64_t nblk = (B_ + 15) / 16;
-    torch::Tensor prof = torch::zeros({nblk, 16}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
+    torch::Tensor prof = torch::zeros({nblk, 16}, torch::TensorOptions().dtype(torch::kInt64).device(device()));
     GcnHeadArgs a = head_;
     a.prof = reinterpret_cast<long long*>(prof.data_ptr<int64_t>());
     step_until_head();
-    ok(eh_gcn_head(&a, stream()), "gcn_head(prof)");
-    if (L_ == 2) ok(eh_gcn_dw(&dw_, dw_blocks_, stream()), "gcn_dw");
-    ok(eh_gcn_reduce(&red_, stream()), "gcn_reduce");
+    launch_ok(eh_gcn_head(&a, cur_stream()), "gcn_head(prof)");
+    if (L_ == 2) launch_ok(eh_gcn_dw(&dw_, dw_blocks_, cur_stream()), "gcn_dw");
+    launch_ok(eh_gcn_reduce(&red_, cur_stream()), "gcn_reduce");
     return prof;
   }
 
   // after a discarded step (overflow / look-back timeout) a node counter may be left
   // non-zero: the trainer clears them with the overflow word
   void reset_counters() {
-    const c10::DeviceGuard guard(dev_);
+    const c10::DeviceGuard guard(device());
     cntw_.zero_();
   }
 
   // one eager step with the head's fp32 root aggregates written out [B][KP] (diagnostics)
   torch::Tensor head_aggregates() {
-    const c10::DeviceGuard guard(dev_);
-    torch::Tensor out = torch::zeros({B_, head_.lin.inp}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    const c10::DeviceGuard guard(device());
+    torch::Tensor out = torch::zeros({B_, head_.lin.inp}, torch::TensorOptions().dtype(torch::kFloat32).device(device()));
     GcnHeadArgs a = head_;
     a.dbg_agg = out.data_ptr<float>();
     step_until_head();
-    ok(eh_gcn_head(&a, stream()), "gcn_head(dbg)");
-    if (L_ == 2) ok(eh_gcn_dw(&dw_, dw_blocks_, stream()), "gcn_dw");
-    ok(eh_gcn_reduce(&red_, stream()), "gcn_reduce");
+    launch_ok(eh_gcn_head(&a, cur_stream()), "gcn_head(dbg)");
+    if (L_ == 2) launch_ok(eh_gcn_dw(&dw_, dw_blocks_, cur_stream()), "gcn_dw");
+    launch_ok(eh_gcn_reduce(&red_, cur_stream()), "gcn_reduce");
     return out;
   }
 
@@ -212,11 +199,9 @@ class GcnPlan {
   int64_t launches() const { return 1 + 3 * L_ + (L_ == 2 ? 2 : 0) + 1 + ndraws_; }
 
  private:
-  py::dict d_;
   int L_ = 0;
   int32_t self_ = 1;
   int64_t B_ = 0, N_ = 0;
-  c10::Device dev_{c10::kCPU};
   GcnGraph g_{};
   std::vector<int64_t> masks_, cap_e_, cap_n_, cap_t_;
   torch::Tensor prob_, alias_, root_rows_, rng_;
@@ -238,33 +223,6 @@ class GcnPlan {
   torch::Tensor dagg_;
   GcnReduceArgs red_{};
   int64_t dw_blocks_ = 0;
-
-  bool has(const char* k) const { return d_.contains(k) && !d_[k].is_none(); }
-  int64_t geti(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "GcnPlan: missing '", k, "'");
-    return d_[k].cast<int64_t>();
-  }
-  std::vector<int64_t> getv(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "GcnPlan: missing '", k, "'");
-    return d_[k].cast<std::vector<int64_t>>();
-  }
-  torch::Tensor T(const char* k) const {
-    TORCH_CHECK(has(k), "GcnPlan: missing tensor '", k, "'");
-    return d_[k].cast<torch::Tensor>();
-  }
-  void need(const torch::Tensor& t, c10::ScalarType st, int64_t numel, const std::string& name) const {
-    TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-    if (dev_.is_cuda()) TORCH_CHECK(t.device() == dev_, name, " must be on the plan's GPU");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-    TORCH_CHECK(t.scalar_type() == st, name, " has dtype ", t.scalar_type(), ", expected ", st);
-    if (numel >= 0) TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(), " elements, expected ", numel);
-  }
-  torch::Tensor zeros(int64_t n, c10::ScalarType st) const {
-    return torch::zeros({n}, torch::TensorOptions().dtype(st).device(dev_));
-  }
-  torch::Tensor full(int64_t n, int64_t v, c10::ScalarType st) const {
-    return torch::full({n}, v, torch::TensorOptions().dtype(st).device(dev_));
-  }
 
   void build_tables() {
     // per-node tables: never cleared (every entry is keyed by the step epoch)
@@ -352,7 +310,7 @@ class GcnPlan {
   // step's layer (GcnLayerDraw); the layer flags are epoch-stamped, never cleared
   void build_layer_draws() {
     if (!has("layer_draws")) return;
-    py::list ld = d_["layer_draws"];
+    py::list ld = item("layer_draws");
     TORCH_CHECK(static_cast<int>(ld.size()) == L_, "GcnPlan: one layer_draws entry per hop");
     for (int h = 0; h < L_; ++h) {
       if (ld[h].is_none()) continue;
@@ -429,11 +387,9 @@ class GcnPlan {
   void build_model() {
     const int64_t D = geti("D"), H0 = geti("H0"), H1 = L_ == 2 ? geti("H1") : 0, E = geti("E"), C = geti("C");
     feat_ = T("features");
+    need_bf16_or_f32(feat_, -1, "features");
     TORCH_CHECK(feat_.dim() == 2 && feat_.size(0) == N_ && feat_.size(1) % 8 == 0 && feat_.size(1) >= D,
                 "GcnPlan: features must be [N, Dpad] with Dpad % 8 == 0");
-    TORCH_CHECK(feat_.scalar_type() == torch::kBFloat16 || feat_.scalar_type() == torch::kFloat32,
-                "GcnPlan: features must be bf16 or fp32");
-    need(feat_, feat_.scalar_type(), -1, "features");
     torch::Tensor labels = T("labels");
     need(labels, torch::kFloat32, N_ * C, "labels");
     GcnAggSrc fsrc{};

@@ -1,35 +1,24 @@
 // torch binding of the fused graph-classification step (graph_cls.hip, graph_cls_args.h).
 //
 // A GraphClsPlan is built once per trainer from a dict of device tensors and sizes
-// (models/graph_cls_trainer.py); it validates every operand, lays out the step kernel's
-// LDS, owns the slab / partial buffers, and step() only launches (hipGraph-capturable: no
-// allocation, no host sync) on torch's current stream: gc_step, then gc_reduce into the
-// flat gradient or — set_optimizer() on one process — into the flat optimizer's update.
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-
+// (models/graph_cls_trainer.py); it validates every operand (PlanDict, binding_util.h), lays
+// out the step kernel's LDS, owns the slab / partial buffers, and step() only launches
+// (hipGraph-capturable: no allocation, no host sync) on torch's current stream: gc_step, then
+// gc_reduce into the flat gradient or — set_optimizer() on one process — into the flat
+// optimizer's update.
 #include <algorithm>
-#include <string>
-#include <vector>
 
+#include "hip/binding_util.h"
 #include "hip/graph_cls_args.h"
 
-namespace py = pybind11;
+using namespace euler_bind;
 using namespace euler_hip;
 
 namespace {
 
-hipStream_t gc_stream() { return c10::hip::getCurrentHIPStream().stream(); }
-
-void gc_ok(hipError_t e, const char* what) {
-  TORCH_CHECK(e == hipSuccess, "euler_amd graph-classification kernel '", what, "' failed: ", hipGetErrorString(e));
-}
-
-class GraphClsPlan {
+class GraphClsPlan : private PlanDict {
  public:
-  explicit GraphClsPlan(py::dict d) : d_(d) {
+  explicit GraphClsPlan(py::dict d) : PlanDict(d, "GraphClsPlan") {
     GcStepArgs& a = a_;
     a.L = static_cast<int32_t>(geti("L"));
     a.B = static_cast<int32_t>(geti("B"));
@@ -57,12 +46,11 @@ class GraphClsPlan {
                 "GraphClsPlan: the embedding table must have 1..", kGcMaxTableRows, " rows and at most ", kGcMaxTable,
                 " elements");
     // graph records, edge pairs of every distinct mask, feature pairs
-    py::list pairs = d_["adj_pair"];
+    py::list pairs = item("adj_pair");
     a.nadj = static_cast<int32_t>(pairs.size());
     TORCH_CHECK(a.nadj >= 1 && a.nadj <= kGcMaxAdj, "GraphClsPlan: 1 to ", kGcMaxAdj, " adjacencies");
     torch::Tensor rec = T("rec");
     need(rec, torch::kInt32, static_cast<int64_t>(a.G) * kGcRec, "rec");
-    dev_ = rec.device();
     for (int j = 0; j < a.nadj; ++j) {
       torch::Tensor pr = pairs[j].cast<torch::Tensor>();
       need(pr, torch::kInt32, -1, "adj_pair");
@@ -94,7 +82,7 @@ class GraphClsPlan {
     a.onehot = onehot.data_ptr<float>();
     a.table = table.data_ptr<float>();
     // parameters
-    py::list W = d_["W"], Wf = d_["Wf"], bl = d_["bl"], eps = d_["eps"];
+    py::list W = item("W"), Wf = item("Wf"), bl = item("bl"), eps = item("eps");
     std::vector<int64_t> oW = getv("o_W"), oWf = getv("o_Wf"), obl = getv("o_bl"), oeps = getv("o_eps");
     TORCH_CHECK(static_cast<int>(W.size()) == a.L && static_cast<int>(oW.size()) == a.L &&
                     static_cast<int>(oWf.size()) == a.L && static_cast<int>(obl.size()) == a.L &&
@@ -143,11 +131,10 @@ class GraphClsPlan {
     a.warm_n = warm.numel();
     // outputs
     a.S = geti("S");
-    auto opt = [&](c10::ScalarType st) { return torch::TensorOptions().dtype(st).device(dev_); };
-    slab_ = torch::zeros({static_cast<int64_t>(a.B) * a.S}, opt(torch::kFloat32));
-    loss_part_ = torch::zeros({a.B}, opt(torch::kFloat32));
-    acc_part_ = torch::zeros({a.B}, opt(torch::kFloat32));
-    gidx_ = torch::zeros({a.B}, opt(torch::kInt32));
+    slab_ = zeros(static_cast<int64_t>(a.B) * a.S, torch::kFloat32);
+    loss_part_ = zeros(a.B, torch::kFloat32);
+    acc_part_ = zeros(a.B, torch::kFloat32);
+    gidx_ = zeros(a.B, torch::kInt32);
     a.slab = slab_.data_ptr<float>();
     a.loss_part = loss_part_.data_ptr<float>();
     a.acc_part = acc_part_.data_ptr<float>();
@@ -177,13 +164,13 @@ class GraphClsPlan {
   }
 
   void step(bool fused_opt) {
-    const c10::DeviceGuard guard(dev_);
+    const c10::DeviceGuard guard(device());
     TORCH_CHECK(!fused_opt || ro_.fuse_opt, "GraphClsPlan: set_optimizer first");
     GcStepArgs a = a_;
     if (fused_opt) a.ostep_inc = const_cast<int64_t*>(ro_.ostep);
-    hipStream_t s = gc_stream();
-    gc_ok(eh_gc_step(&a, s), "gc_step");
-    gc_ok(eh_gc_reduce(fused_opt ? &ro_ : &r_, s), "gc_reduce");
+    hipStream_t s = cur_stream();
+    launch_ok(eh_gc_step(&a, s), "gc_step");
+    launch_ok(eh_gc_reduce(fused_opt ? &ro_ : &r_, s), "gc_reduce");
   }
 
   // the flat optimizer of one process's step: {flat, m, v, step, kind, lr, b1, b2, eps, wd,
@@ -216,12 +203,12 @@ class GraphClsPlan {
 
   // one eager step (no optimizer) with per-block phase stamps [B][32] (diagnostics)
   torch::Tensor profile() {
-    const c10::DeviceGuard guard(dev_);
-    torch::Tensor prof = torch::zeros({a_.B, 32}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
+    const c10::DeviceGuard guard(device());
+    torch::Tensor prof = torch::zeros({a_.B, 32}, torch::TensorOptions().dtype(torch::kInt64).device(device()));
     GcStepArgs a = a_;
     a.prof = reinterpret_cast<long long*>(prof.data_ptr<int64_t>());
-    gc_ok(eh_gc_step(&a, gc_stream()), "gc_step(prof)");
-    gc_ok(eh_gc_reduce(&r_, gc_stream()), "gc_reduce");
+    launch_ok(eh_gc_step(&a, cur_stream()), "gc_step(prof)");
+    launch_ok(eh_gc_reduce(&r_, cur_stream()), "gc_reduce");
     return prof;
   }
   torch::Tensor gidx() const { return gidx_; }
@@ -229,8 +216,6 @@ class GraphClsPlan {
   bool z_kept() const { return a_.zst != 0; }
 
  private:
-  py::dict d_;
-  c10::Device dev_{c10::kCPU};
   GcStepArgs a_{};
   GcReduceArgs r_{}, ro_{};
   std::vector<torch::Tensor> keep_, opt_keep_;
@@ -272,27 +257,6 @@ class GraphClsPlan {
     a.zst = off + (a.L - 1) * z1 <= max_lds_ ? 1 : 0;
     if (a.zst) off += (a.L - 1) * ((z1 + 15) / 16 * 16);
     a.lds_bytes = static_cast<int32_t>(off);
-  }
-
-  bool has(const char* k) const { return d_.contains(k) && !d_[k].is_none(); }
-  int64_t geti(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "GraphClsPlan: missing '", k, "'");
-    return d_[k].cast<int64_t>();
-  }
-  std::vector<int64_t> getv(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "GraphClsPlan: missing '", k, "'");
-    return d_[k].cast<std::vector<int64_t>>();
-  }
-  torch::Tensor T(const char* k) const {
-    TORCH_CHECK(has(k), "GraphClsPlan: missing tensor '", k, "'");
-    return d_[k].cast<torch::Tensor>();
-  }
-  void need(const torch::Tensor& t, c10::ScalarType st, int64_t numel, const std::string& name) const {
-    TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-    if (dev_.is_cuda()) TORCH_CHECK(t.device() == dev_, name, " must be on the plan's GPU");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-    TORCH_CHECK(t.scalar_type() == st, name, " has dtype ", t.scalar_type(), ", expected ", st);
-    if (numel >= 0) TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(), " elements, expected ", numel);
   }
 };
 

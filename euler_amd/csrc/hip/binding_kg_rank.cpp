@@ -1,38 +1,24 @@
-// torch binding of the link-prediction rank kernels (kg_rank.hip).  Host-only, same rules as
-// binding.cpp: every operand is validated (dtype, device, contiguity and the element counts
-// the grids assume) before a launch; launches go to torch's current HIP stream.  The outputs
-// are allocated here, never inside a launcher.
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-
+// torch binding of the link-prediction rank kernels (kg_rank.hip).  Host-only; operands go
+// through binding_util.h (rules R1-R3 there).  The outputs are allocated here, never inside a
+// launcher.
+#include "hip/binding_util.h"
 #include "hip/launchers.h"
 
-namespace py = pybind11;
+using namespace euler_bind;
 
 namespace {
-
-hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
-
-void ok(hipError_t e, const char* what) {
-  TORCH_CHECK(e == hipSuccess, "euler_amd HIP kernel '", what, "' failed: ", hipGetErrorString(e));
-}
-
-void typed(const torch::Tensor& t, c10::ScalarType st, const char* name, const torch::Tensor& like) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous GPU tensor");
-  TORCH_CHECK(t.scalar_type() == st, name, " has dtype ", t.scalar_type(), ", expected ", st);
-  TORCH_CHECK(t.device() == like.device(), name, " is on another device");
-}
 
 // (better [B], ties [B]) int64 of q [B, d] against cands [N, d]; kind 0 l1 / 1 l2 / 2 dot;
 // filt_ptr [B + 1] int64 + filt_idx int32 (ascending inside a list) or both None
 std::vector<torch::Tensor> kg_rank_counts(torch::Tensor q, torch::Tensor cands, torch::Tensor true_idx, int64_t kind,
                                           c10::optional<torch::Tensor> filt_ptr,
                                           c10::optional<torch::Tensor> filt_idx, int64_t splits) {
-  typed(q, torch::kFloat32, "q", q);
-  typed(cands, torch::kFloat32, "cands", q);
-  typed(true_idx, torch::kInt64, "true_idx", q);
+  const Operands c("kg_rank_counts", q, "q");
+  c.f32(q, "q");
+  c.f32(cands, "cands");
+  c.i64(true_idx, "true_idx");
+  c.i64(filt_ptr, "filt_ptr");
+  c.i32(filt_idx, "filt_idx");
   TORCH_CHECK(kind >= 0 && kind <= 2, "kg_rank_counts: kind must be 0 (l1), 1 (l2) or 2 (dot)");
   TORCH_CHECK(q.dim() == 2 && cands.dim() == 2 && q.size(1) == cands.size(1) && q.size(1) >= 1,
               "kg_rank_counts: q [B, d] and cands [N, d] must share d >= 1");
@@ -48,8 +34,6 @@ std::vector<torch::Tensor> kg_rank_counts(torch::Tensor q, torch::Tensor cands, 
   const int32_t* fi = nullptr;
   int64_t nf = 0;
   if (filt_ptr.has_value()) {
-    typed(*filt_ptr, torch::kInt64, "filt_ptr", q);
-    typed(*filt_idx, torch::kInt32, "filt_idx", q);
     TORCH_CHECK(filt_ptr->dim() == 1 && filt_ptr->numel() == B + 1, "kg_rank_counts: filt_ptr must be [B + 1], got ",
                 filt_ptr->numel(), " entries for B = ", B);
     TORCH_CHECK(filt_idx->dim() == 1, "kg_rank_counts: filt_idx must be one-dimensional");
@@ -57,7 +41,7 @@ std::vector<torch::Tensor> kg_rank_counts(torch::Tensor q, torch::Tensor cands, 
     nf = filt_idx->numel();
     fi = nf > 0 ? filt_idx->data_ptr<int32_t>() : nullptr;
   }
-  const c10::DeviceGuard g(q.device());
+  const auto g = c.guard();
   {
     // a position outside cands has no score to rank against
     const auto mm = torch::stack({true_idx.min(), true_idx.max()}).cpu();
@@ -67,13 +51,13 @@ std::vector<torch::Tensor> kg_rank_counts(torch::Tensor q, torch::Tensor cands, 
   auto ts = torch::empty({B}, q.options());
   auto pb = torch::empty({B, splits}, q.options().dtype(torch::kInt64));
   auto pt = torch::empty({B, splits}, q.options().dtype(torch::kInt64));
-  ok(eh_kg_rank_true(q.data_ptr<float>(), cands.data_ptr<float>(), true_idx.data_ptr<int64_t>(), B, N,
-                     static_cast<int>(q.size(1)), static_cast<int>(kind), ts.data_ptr<float>(), stream()),
-     "kg_rank_true");
-  ok(eh_kg_rank_scan(q.data_ptr<float>(), cands.data_ptr<float>(), true_idx.data_ptr<int64_t>(), ts.data_ptr<float>(),
-                     fp, fi, nf, B, N, static_cast<int>(q.size(1)), static_cast<int>(kind), static_cast<int>(splits),
-                     pb.data_ptr<int64_t>(), pt.data_ptr<int64_t>(), stream()),
-     "kg_rank_scan");
+  launch_ok(eh_kg_rank_true(q.data_ptr<float>(), cands.data_ptr<float>(), true_idx.data_ptr<int64_t>(), B, N,
+                            static_cast<int>(q.size(1)), static_cast<int>(kind), ts.data_ptr<float>(), cur_stream()),
+            "kg_rank_true");
+  launch_ok(eh_kg_rank_scan(q.data_ptr<float>(), cands.data_ptr<float>(), true_idx.data_ptr<int64_t>(),
+                            ts.data_ptr<float>(), fp, fi, nf, B, N, static_cast<int>(q.size(1)), static_cast<int>(kind),
+                            static_cast<int>(splits), pb.data_ptr<int64_t>(), pt.data_ptr<int64_t>(), cur_stream()),
+            "kg_rank_scan");
   return {pb.sum(1), pt.sum(1)};
 }
 

@@ -1,29 +1,12 @@
-// torch binding of the full-neighbourhood GraphSAGE layer (sage_csr.hip).  Host-only, same
-// rules as binding.cpp: every operand is validated (dtype, device, contiguity and the element
-// counts the kernel assumes) before the launch, which goes to torch's current HIP stream.  The
-// output is allocated here (or is the caller's table slice), never inside the launcher.
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-
+// torch binding of the full-neighbourhood GraphSAGE layer (sage_csr.hip).  Host-only; operands
+// go through binding_util.h (rules R1-R3 there).  The output is allocated here (or is the
+// caller's table slice), never inside the launcher.
+#include "hip/binding_util.h"
 #include "hip/launchers.h"
 
-namespace py = pybind11;
+using namespace euler_bind;
 
 namespace {
-
-hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
-
-void ok(hipError_t e, const char* what) {
-  TORCH_CHECK(e == hipSuccess, "euler_amd HIP kernel '", what, "' failed: ", hipGetErrorString(e));
-}
-
-void typed(const torch::Tensor& t, c10::ScalarType st, const char* name, const torch::Tensor& like) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous GPU tensor");
-  TORCH_CHECK(t.scalar_type() == st, name, " has dtype ", t.scalar_type(), ", expected ", st);
-  TORCH_CHECK(t.device() == like.device(), name, " is on another device");
-}
 
 // out [M, Hp] = act([x[r] | nbr_scale * wmean_{masked edges of r} x + self_scale * x[r]] @ W^T) for
 // r = rows[m] (rows None: r = m, M = N) on the CSR (indptr [N T + 1], nbr [E], cumw [E])
@@ -31,13 +14,13 @@ torch::Tensor sage_csr_fwd(torch::Tensor indptr, torch::Tensor nbr, torch::Tenso
                            int64_t mask, torch::Tensor x, torch::Tensor W, c10::optional<torch::Tensor> rows,
                            double nbr_scale, double self_scale, bool relu, bool out_fp32,
                            c10::optional<torch::Tensor> out_opt) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, "sage_csr_fwd: x must be a contiguous GPU [N, Dp]");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 || x.scalar_type() == torch::kFloat32,
-              "sage_csr_fwd: x must be bf16 or fp32, got ", x.scalar_type());
-  typed(indptr, torch::kInt64, "indptr", x);
-  typed(nbr, torch::kInt32, "nbr", x);
-  typed(cumw, torch::kFloat32, "cumw", x);
-  typed(W, torch::kBFloat16, "W", x);
+  const Operands c("sage_csr_fwd", x, "x");
+  c.bf16_or_f32(x, "x");
+  TORCH_CHECK(x.dim() == 2, "sage_csr_fwd: x must be [N, Dp]");
+  c.i64(indptr, "indptr");
+  c.i32(nbr, "nbr");
+  c.f32(cumw, "cumw");
+  c.bf16(W, "W");
   const int64_t N = x.size(0), Dp = x.size(1);
   TORCH_CHECK(num_types >= 1 && num_types <= 32, "sage_csr_fwd: 1 to 32 edge types, got ", num_types);
   TORCH_CHECK(mask >= 0 && mask <= 0xFFFFFFFFLL, "sage_csr_fwd: mask is a 32-bit edge-type set");
@@ -54,28 +37,30 @@ torch::Tensor sage_csr_fwd(torch::Tensor indptr, torch::Tensor nbr, torch::Tenso
   const int32_t* rp = nullptr;
   int64_t M = N;
   if (rows.has_value()) {
-    typed(*rows, torch::kInt32, "rows", x);
+    c.i32(*rows, "rows");
     TORCH_CHECK(rows->dim() == 1, "sage_csr_fwd: rows must be one-dimensional");
     M = rows->numel();
     rp = M > 0 ? rows->data_ptr<int32_t>() : nullptr;
   }
-  const c10::DeviceGuard g(x.device());
   torch::Tensor out;
   if (out_opt.has_value()) {  // the caller's slice of a layer table
     out = *out_opt;
-    typed(out, out_fp32 ? torch::kFloat32 : torch::kBFloat16, "out", x);
+    c.is(out, out_fp32 ? torch::kFloat32 : torch::kBFloat16, "out");
     TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == Hp, "sage_csr_fwd: out must be [", M, ", ", Hp,
                 "]");
-  } else {
+  }
+  const auto g = c.guard();
+  if (!out_opt.has_value()) {
     out = torch::empty({M, Hp}, x.options().dtype(out_fp32 ? torch::kFloat32 : torch::kBFloat16));
   }
   if (M == 0) return out;
-  ok(eh_sage_csr_fwd(indptr.data_ptr<int64_t>(), nbr.numel() ? nbr.data_ptr<int32_t>() : nullptr,
-                     cumw.numel() ? cumw.data_ptr<float>() : nullptr, N, nbr.numel(), static_cast<int>(num_types),
-                     static_cast<uint32_t>(mask), x.data_ptr(), x.scalar_type() == torch::kFloat32 ? 1 : 0,
-                     static_cast<int>(Dp), rp, M, W.data_ptr(), static_cast<int>(Hp), static_cast<float>(nbr_scale),
-                     static_cast<float>(self_scale), relu ? 1 : 0, out.data_ptr(), out_fp32 ? 1 : 0, stream()),
-     "sage_csr_fwd");
+  launch_ok(eh_sage_csr_fwd(indptr.data_ptr<int64_t>(), nbr.numel() ? nbr.data_ptr<int32_t>() : nullptr,
+                            cumw.numel() ? cumw.data_ptr<float>() : nullptr, N, nbr.numel(),
+                            static_cast<int>(num_types), static_cast<uint32_t>(mask), x.data_ptr(),
+                            x.scalar_type() == torch::kFloat32 ? 1 : 0, static_cast<int>(Dp), rp, M, W.data_ptr(),
+                            static_cast<int>(Hp), static_cast<float>(nbr_scale), static_cast<float>(self_scale),
+                            relu ? 1 : 0, out.data_ptr(), out_fp32 ? 1 : 0, cur_stream()),
+            "sage_csr_fwd");
   return out;
 }
 

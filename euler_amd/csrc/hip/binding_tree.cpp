@@ -1,28 +1,20 @@
 // torch binding of the fused GraphSAGE tree step (sage_tree.hip).
 //
 // A TreePlan is built once per trainer from a dict of device tensors and sizes: every
-// operand is validated here (dtype, device, contiguity and the exact element count the
-// kernels' grids assume), the kernel argument blocks are filled once, and the per-step
-// methods only launch on torch's current stream (hipGraph-capturable, no allocation,
-// no host sync, no per-call Python marshalling).
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-
+// operand is validated here (PlanDict, binding_util.h: dtype, device, contiguity and the exact
+// element count the kernels' grids assume), the kernel argument blocks are filled once, and
+// the per-step methods only launch on torch's current stream (hipGraph-capturable, no
+// allocation, no host sync, no per-call Python marshalling).
 #include <cstdio>
 #include <cstdlib>
-#include <string>
-#include <vector>
 
+#include "hip/binding_util.h"
 #include "hip/tree_args.h"
 
-namespace py = pybind11;
+using namespace euler_bind;
 using namespace euler_hip;
 
 namespace {
-
-hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 // EULER_AMD_TREE_SYNC=1: synchronise after every launch and name the kernel that failed
 // (debugging aid; never set it for timing or graph capture)
@@ -34,18 +26,52 @@ bool sync_debug() {
   return on;
 }
 
-void ok(hipError_t e, const char* what) {
-  TORCH_CHECK(e == hipSuccess, "euler_amd tree kernel '", what, "' failed: ", hipGetErrorString(e));
+void tree_ok(hipError_t e, const char* what) {
+  launch_ok(e, what);
   if (sync_debug()) {
-    const hipError_t s = hipStreamSynchronize(c10::hip::getCurrentHIPStream().stream());
+    const hipError_t s = hipStreamSynchronize(cur_stream());
     TORCH_CHECK(s == hipSuccess, "euler_amd tree kernel '", what, "' faulted: ", hipGetErrorString(s));
     fprintf(stderr, "[tree-sync] %s ok\n", what);
   }
 }
 
-class TreePlan {
+// The sampled graph (CSR, root alias table) and the sampler fields of the tree, from the keys
+// every tree-sampling plan shares: indptr, num_types, nbr, cumw, node_prob, node_alias,
+// root_rows (optional), rng.  F / logP / m: fan-out, slot-group bits and edge mask of hops 1, 2
+void fill_graph_tree(PlanDict& pd, TrGraph& g, TrTree& tr, int64_t F1, int64_t F2, int64_t logP1, int64_t logP2,
+                     uint32_t m1, uint32_t m2) {
+  torch::Tensor indptr = pd.T("indptr"), rng = pd.T("rng");
+  pd.need(indptr, torch::kInt64, -1, "indptr");
+  pd.need(rng, torch::kInt64, 2, "rng");
+  const int64_t nt = pd.geti("num_types");
+  TORCH_CHECK(nt >= 1 && nt <= 32 && (indptr.numel() - 1) % nt == 0, pd.name(), ": indptr must be [N*T+1]");
+  g.indptr = indptr.data_ptr<int64_t>();
+  g.num_types = static_cast<int32_t>(nt);
+  g.num_rows = (indptr.numel() - 1) / nt;
+  torch::Tensor nbr = pd.T("nbr"), cumw = pd.T("cumw"), prob = pd.T("node_prob");
+  pd.need(nbr, torch::kInt32, -1, "nbr");
+  pd.need(cumw, torch::kFloat32, nbr.numel(), "cumw");
+  g.nbr = nbr.data_ptr<int32_t>();
+  g.cumw = cumw.data_ptr<float>();
+  pd.need(prob, torch::kFloat32, -1, "node_prob");
+  g.pop = prob.numel();
+  TORCH_CHECK(g.pop > 0, pd.name(), ": empty root population");
+  g.prob = prob.data_ptr<float>();
+  g.alias = pd.i32("node_alias", g.pop);
+  // candidate -> row map of the root sampler (node-type subset)
+  g.root_rows = pd.has("root_rows") ? pd.i32("root_rows", g.pop) : nullptr;
+  tr.rng = rng.data_ptr<int64_t>();
+  tr.F1 = static_cast<int32_t>(F1);
+  tr.F2 = static_cast<int32_t>(F2);
+  tr.logP1 = static_cast<int32_t>(logP1);
+  tr.logP2 = static_cast<int32_t>(logP2);
+  tr.m1 = m1;
+  tr.m2 = m2;
+}
+
+class TreePlan : private PlanDict {
  public:
-  explicit TreePlan(py::dict d) : d_(d) {
+  explicit TreePlan(py::dict d) : PlanDict(d, "TreePlan") {
     L_ = geti("L");
     B_ = geti("B");
     TORCH_CHECK(L_ >= 1 && L_ <= 3, "TreePlan: 1..3 hops");
@@ -62,8 +88,6 @@ class TreePlan {
     C_ = geti("C");
     C_real_ = geti("C_real");
     self_ = geti("include_self");
-    dev_ = T("rng").device();
-    TORCH_CHECK(dev_.is_cuda(), "TreePlan: tensors must be on the GPU");
     for (int k = 1; k < L_; ++k) TORCH_CHECK(logP_[k] >= 4 && (1 << logP_[k]) > F_[k], "TreePlan: slot group too small");
     for (int k = 0; k < L_; ++k) TORCH_CHECK(dims_[k] % 64 == 0, "TreePlan: conv widths must be padded to 64");
     TORCH_CHECK(D_ % 16 == 0 && E_ % 32 == 0 && C_ % 32 == 0 && C_real_ <= C_, "TreePlan: padded dims");
@@ -72,7 +96,9 @@ class TreePlan {
     M_[0] = B_;
     for (int k = 1; k < L_; ++k) M_[k] = M_[k - 1] << logP_[k];
     if (has("dw_route_impl")) route_impl_ = static_cast<int>(geti("dw_route_impl"));
-    build_graph();
+    fill_graph_tree(*this, graph_, tree_, L_ > 1 ? F_[1] : 0, L_ > 2 ? F_[2] : 0, L_ > 1 ? logP_[1] : 0,
+                    L_ > 2 ? logP_[2] : 0, static_cast<uint32_t>(masks_[1]),
+                    L_ > 2 ? static_cast<uint32_t>(masks_[2]) : 0u);
     build_fwd();
     build_comb();
     build_head();
@@ -81,27 +107,27 @@ class TreePlan {
   }
 
   void sample() {
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_sample(&sample_, stream()), "tr_sample");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_sample(&sample_, cur_stream()), "tr_sample");
   }
 
   // gemm_only (pipelined step): layer 0 from the A rows the previous optimizer launch's
   // gather blocks wrote (opt(..., with_gather=True))
   void fwd(c10::optional<torch::Tensor> prof, bool gemm_only) {
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TORCH_CHECK(!gemm_only || pipeline_ok(), "TreePlan: no pipelined forward for this plan");
     TrFwdArgs a0 = fwd0_;
     if (prof.has_value()) {
       need(*prof, torch::kInt64, (fwd0_.M / (gemm_only ? 64 : bm0_)) * 8, "prof");
       a0.prof = reinterpret_cast<long long*>(prof->data_ptr<int64_t>());
     }
-    ok(eh_tr_fwd(&a0, gemm_only ? 3 : (L_ == 1 ? 1 : 0), feat_fp32_, bm0_, stream()), "tr_fwd");
-    if (L_ == 3) ok(eh_tr_fwd(&fwd1_, 2, 0, bm1_, stream()), "tr_fwd(inner)");
+    tree_ok(eh_tr_fwd(&a0, gemm_only ? 3 : (L_ == 1 ? 1 : 0), feat_fp32_, bm0_, cur_stream()), "tr_fwd");
+    if (L_ == 3) tree_ok(eh_tr_fwd(&fwd1_, 2, 0, bm1_, cur_stream()), "tr_fwd(inner)");
   }
 
   // with_sample: extra blocks of the launch draw the next step's batch
   void head(c10::optional<torch::Tensor> prof, bool with_sample) {
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TrHeadArgs a = head_;
     if (with_sample) {
       a.smp = sample_;
@@ -111,22 +137,22 @@ class TreePlan {
       need(*prof, torch::kInt64, (B_ / kTrHeadRows) * 8, "prof");
       a.prof = reinterpret_cast<long long*>(prof->data_ptr<int64_t>());
     }
-    ok(eh_tr_head(&a, B_, stream()), "tr_head");
+    tree_ok(eh_tr_head(&a, B_, cur_stream()), "tr_head");
   }
 
   void bwd() {
     if (L_ != 3) return;
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_bwd(&bwd1_, stream()), "tr_bwd");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_bwd(&bwd1_, cur_stream()), "tr_bwd");
   }
 
   // dW of the given problems, one launch: routed problems first, the others grouped
   void dw(std::vector<int64_t> which, c10::optional<torch::Tensor> prof) {
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TrDwLaunch L{};
     L.route_impl = route_impl_;
     if (prof.has_value()) {
-      TORCH_CHECK(prof->dtype() == torch::kInt64 && prof->is_cuda() && prof->is_contiguous(), "dw: prof");
+      need(*prof, torch::kInt64, -1, "prof");
       L.prof = reinterpret_cast<long long*>(prof->data_ptr<int64_t>());
     }
     for (int64_t i : which) {
@@ -140,7 +166,7 @@ class TreePlan {
       }
     }
     if (L.nroute == 0 && L.plain.n == 0) return;
-    ok(eh_tr_dw(&L, stream()), "tr_dw");
+    tree_ok(eh_tr_dw(&L, cur_stream()), "tr_dw");
   }
 
   std::vector<int64_t> problems(bool route) const {
@@ -155,7 +181,7 @@ class TreePlan {
   // with_gather: extra blocks gather the NEXT step's layer-0 inputs (the tree the head's
   // sampler drew) into A0_kt and A0_rows, so that step's forward is GEMM-only
   void opt(int64_t mode, double grad_scale, bool with_sample, bool with_gather) {
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TORCH_CHECK(!with_gather || pipeline_ok(), "TreePlan: no pipelined gather for this plan");
     TrOptArgs a = opt_;
     a.grad_scale = static_cast<float>(grad_scale);
@@ -175,7 +201,7 @@ class TreePlan {
       }();
       a.opt_tpb = tpb;
     }
-    ok(eh_tr_opt(&a, static_cast<int>(mode), stream()), "tr_opt");
+    tree_ok(eh_tr_opt(&a, static_cast<int>(mode), cur_stream()), "tr_opt");
   }
 
   // the pipelined step applies: 2 hops, the 64-row layer-0 kernel, A0_rows given, sibling
@@ -191,7 +217,7 @@ class TreePlan {
   void opt_segments(int64_t mode, std::vector<int64_t> segs, bool head_stats) {
     TORCH_CHECK(mode == 0, "opt_segments: only the reduce (mode 0) runs on a segment subset");
     TORCH_CHECK(!segs.empty() && (int64_t)segs.size() <= opt_.nseg, "opt_segments: bad segment list");
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TrOptArgs a = opt_;
     int blk = 0, n = 0;
     for (int64_t k : segs) {
@@ -205,7 +231,7 @@ class TreePlan {
     a.nblk = blk;
     a.nsample = 0;
     if (!head_stats) a.nhead = 0;
-    ok(eh_tr_opt(&a, 0, stream()), "tr_opt(segments)");
+    tree_ok(eh_tr_opt(&a, 0, cur_stream()), "tr_opt(segments)");
   }
 
   int64_t fwd_blocks() const { return fwd0_.M / bm0_; }
@@ -214,8 +240,7 @@ class TreePlan {
   // the flat fp32 gradient the reduce launch writes and the optimizer reads (e.g. a view of
   // the xGMI all-reduce's IPC input region, so the all-reduce runs in place there)
   void set_grad(torch::Tensor g) {
-    TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kFloat32 && g.is_contiguous() && g.numel() == opt_.n,
-                "grad must be a contiguous fp32 GPU tensor of the flat parameter size");
+    need(g, torch::kFloat32, opt_.n, "grad");
     grad_ = g;
     opt_.g = g.data_ptr<float>();
   }
@@ -225,9 +250,7 @@ class TreePlan {
       g16_ = torch::Tensor();
       return;
     }
-    TORCH_CHECK(g16->is_cuda() && g16->scalar_type() == torch::kBFloat16 && g16->is_contiguous() &&
-                    g16->numel() == opt_.n,
-                "grad16 must be a contiguous bf16 GPU tensor of the flat parameter size");
+    need(*g16, torch::kBFloat16, opt_.n, "grad16");
     g16_ = *g16;
     opt_.g16 = reinterpret_cast<uint16_t*>(g16_.data_ptr());
   }
@@ -244,13 +267,11 @@ class TreePlan {
   }
 
  private:
-  py::dict d_;
   int L_, B_, D_, E_, C_, C_real_, self_;
   int feat_fp32_ = 0, bm0_ = 32, bm1_ = 32;
   int route_impl_ = 0;  // EULER_AMD_DW_ROUTE_IMPL / plan key dw_route_impl
   bool cached_ = false;
   std::vector<int64_t> F_, logP_, masks_, dims_, M_;
-  c10::Device dev_{c10::kCPU};
   TrGraph graph_{};
   TrTree tree_{};
   TrSampleArgs sample_{};
@@ -258,85 +279,20 @@ class TreePlan {
   TrHeadArgs head_{};
   TrBwdArgs bwd1_{};
   std::vector<TrDwProb> probs_;
-  std::vector<torch::Tensor> owned_;
   torch::Tensor roots_cur_;  // the forward's copy of the batch's roots (read by the head)
   TrOptArgs opt_{};
   torch::Tensor g16_, grad_;
 
-  bool has(const char* k) const { return d_.contains(k) && !d_[k].is_none(); }
-  int64_t geti(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "TreePlan: missing '", k, "'");
-    return d_[k].cast<int64_t>();
-  }
-  double getf(const char* k) const { return d_[k].cast<double>(); }
-  std::vector<int64_t> getv(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "TreePlan: missing '", k, "'");
-    return d_[k].cast<std::vector<int64_t>>();
-  }
-  torch::Tensor T(const char* k) const {
-    TORCH_CHECK(has(k), "TreePlan: missing tensor '", k, "'");
-    return d_[k].cast<torch::Tensor>();
-  }
-  torch::Tensor Tk(const std::string& k) const { return T(k.c_str()); }
-  void need(const torch::Tensor& t, c10::ScalarType st, int64_t numel, const std::string& name) const {
-    TORCH_CHECK(t.is_cuda() && t.device() == dev_, name, " must be on the trainer's GPU");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-    TORCH_CHECK(t.scalar_type() == st, name, " has the wrong dtype");
-    if (numel >= 0) TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(), " elements, expected ", numel);
-  }
-  template <typename P>
-  P* ptr(const std::string& k, c10::ScalarType st, int64_t numel) {
-    torch::Tensor t = Tk(k);
-    need(t, st, numel, k);
-    return reinterpret_cast<P*>(t.data_ptr());
-  }
-  uint16_t* bf(const std::string& k, int64_t numel) { return ptr<uint16_t>(k, torch::kBFloat16, numel); }
-  float* f32(const std::string& k, int64_t numel) { return ptr<float>(k, torch::kFloat32, numel); }
-  int32_t* i32(const std::string& k, int64_t numel) { return ptr<int32_t>(k, torch::kInt32, numel); }
-
   int64_t Hin(int k) const { return k == 0 ? D_ : dims_[k - 1]; }
-
-  void build_graph() {
-    torch::Tensor indptr = T("indptr"), rng = T("rng");
-    need(indptr, torch::kInt64, -1, "indptr");
-    need(rng, torch::kInt64, 2, "rng");
-    const int64_t T_ = geti("num_types");
-    TORCH_CHECK(T_ >= 1 && T_ <= 32 && (indptr.numel() - 1) % T_ == 0, "TreePlan: indptr must be [N*T+1]");
-    graph_.indptr = indptr.data_ptr<int64_t>();
-    graph_.num_types = static_cast<int32_t>(T_);
-    graph_.num_rows = (indptr.numel() - 1) / T_;
-    torch::Tensor nbr = T("nbr"), cumw = T("cumw");
-    need(nbr, torch::kInt32, -1, "nbr");
-    need(cumw, torch::kFloat32, nbr.numel(), "cumw");
-    graph_.nbr = nbr.data_ptr<int32_t>();
-    graph_.cumw = cumw.data_ptr<float>();
-    torch::Tensor prob = T("node_prob");
-    need(prob, torch::kFloat32, -1, "node_prob");
-    graph_.pop = prob.numel();
-    TORCH_CHECK(graph_.pop > 0, "TreePlan: empty root population");
-    graph_.prob = prob.data_ptr<float>();
-    graph_.alias = i32("node_alias", graph_.pop);
-    graph_.root_rows = has("root_rows") ? i32("root_rows", graph_.pop) : nullptr;
-    tree_.rng = rng.data_ptr<int64_t>();
-    tree_.F1 = L_ > 1 ? static_cast<int32_t>(F_[1]) : 0;
-    tree_.F2 = L_ > 2 ? static_cast<int32_t>(F_[2]) : 0;
-    tree_.logP1 = L_ > 1 ? static_cast<int32_t>(logP_[1]) : 0;
-    tree_.logP2 = L_ > 2 ? static_cast<int32_t>(logP_[2]) : 0;
-    tree_.m1 = static_cast<uint32_t>(masks_[1]);
-    tree_.m2 = L_ > 2 ? static_cast<uint32_t>(masks_[2]) : 0u;
-  }
 
   void build_fwd() {
     // "fwd_features" (+ "fwd_nodes" / "fwd_leaf" cache positions): the forward gathers from
     // a feature cache filled by the sharded-feature exchange instead of the whole table
     const bool cached = has("fwd_features");
     torch::Tensor x = cached ? T("fwd_features") : T("features");
+    feat_fp32_ = !need_bf16_or_f32(x, -1, "features");
     TORCH_CHECK(x.dim() == 2 && x.size(1) == D_, "features must be [N, D] with D padded to 16");
     TORCH_CHECK(cached || x.size(0) == graph_.num_rows, "features must have one row per graph row");
-    TORCH_CHECK(x.scalar_type() == torch::kBFloat16 || x.scalar_type() == torch::kFloat32,
-                "features must be bf16 or fp32");
-    need(x, x.scalar_type(), -1, "features");
-    feat_fp32_ = x.scalar_type() == torch::kFloat32;
     const int lv = L_ - 1;           // level of layer 0's target rows
     const int64_t M = M_[lv];
     TrSampleArgs& sm = sample_;
@@ -361,7 +317,7 @@ class TreePlan {
     a.nodes = cached ? i32("fwd_nodes", M) : sm.nodes;
     a.leaf = cached ? i32("fwd_leaf", M * sm.FL) : sm.leaf;
     a.roots_in = sm.roots;
-    roots_cur_ = torch::zeros({B_}, torch::TensorOptions().dtype(torch::kInt32).device(dev_));
+    roots_cur_ = zeros(B_, torch::kInt32);
     a.roots_cur = roots_cur_.data_ptr<int32_t>();
     a.B = B_;
     a.step = ptr<int64_t>("step", torch::kInt64, 1);
@@ -386,7 +342,7 @@ class TreePlan {
     TORCH_CHECK(M % bm0_ == 0, "TreePlan: target rows must be a multiple of the fwd block rows");
     if (L_ == 3) {
       TrFwdArgs& b = fwd1_;
-      b.x = Tk("A1").data_ptr();
+      b.x = T("A1").data_ptr();
       b.D = static_cast<int32_t>(dims_[0]);
       b.M = M_[1];
       b.include_self = self_;
@@ -422,22 +378,10 @@ class TreePlan {
     c.C = C_;
     c.E = E_;
     c.H = static_cast<int32_t>(H);
-    c.Wc = owned_bf16((int64_t)C_ * H);
-    c.WcT = owned_bf16((int64_t)C_ * H);
-    c.bc = owned(C_);
+    c.Wc = zeros_ptr<uint16_t>((int64_t)C_ * H, torch::kBFloat16);
+    c.WcT = zeros_ptr<uint16_t>((int64_t)C_ * H, torch::kBFloat16);
+    c.bc = zeros_ptr<float>(C_, torch::kFloat32);
     fwd0_.ncomb = 1;
-  }
-
-  uint16_t* owned_bf16(int64_t n) {
-    torch::Tensor t = torch::zeros({n}, torch::TensorOptions().dtype(torch::kBFloat16).device(dev_));
-    owned_.push_back(t);
-    return reinterpret_cast<uint16_t*>(t.data_ptr());
-  }
-
-  float* owned(int64_t n) {  // plan-owned fp32 scratch
-    torch::Tensor t = torch::zeros({n}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    owned_.push_back(t);
-    return t.data_ptr<float>();
   }
 
   uint32_t* i32_as_u32(const std::string& k, int64_t numel) { return reinterpret_cast<uint32_t*>(i32(k, numel)); }
@@ -465,17 +409,17 @@ class TreePlan {
     a.roots = fwd0_.roots_cur;
     const int mode = static_cast<int>(geti("label_mode"));
     torch::Tensor lab = T("labels");
-    TORCH_CHECK(lab.is_cuda() && lab.is_contiguous() && lab.device() == dev_, "labels must be contiguous on the GPU");
+    need_any(lab, "labels");
     TORCH_CHECK(mode >= 0 && mode <= 2, "label_mode must be 0, 1 or 2");
     // "label_rows": a label table over other rows than the graph's (the row-sharded trainer
     // hands the head a [B] table of the batch's labels with roots = 0 .. B-1)
     const int64_t lrows = has("label_rows") ? geti("label_rows") : graph_.num_rows;
     if (mode == 0) {
-      TORCH_CHECK(lab.scalar_type() == torch::kInt16 && lab.numel() == lrows, "labels int16 [N]");
+      TORCH_CHECK(lab.scalar_type() == torch::kInt16 && lab.numel() == lrows, "TreePlan: labels int16 [N]");
     } else if (mode == 1) {
-      TORCH_CHECK(lab.scalar_type() == torch::kInt32 && lab.numel() == lrows, "labels int32 [N]");
+      TORCH_CHECK(lab.scalar_type() == torch::kInt32 && lab.numel() == lrows, "TreePlan: labels int32 [N]");
     } else {
-      TORCH_CHECK(lab.scalar_type() == torch::kBFloat16 && lab.numel() == lrows * C_, "labels bf16 [N, C]");
+      TORCH_CHECK(lab.scalar_type() == torch::kBFloat16 && lab.numel() == lrows * C_, "TreePlan: labels bf16 [N, C]");
     }
     a.labels = lab.data_ptr();
     a.label_mode = mode;
@@ -488,8 +432,8 @@ class TreePlan {
     a.g_kt = bf("g_kt", B_ * H);
     a.dA = L_ > 1 ? f32("dA" + std::to_string(last), B_ * Hin2) : nullptr;
     const int64_t nblk = B_ / kTrHeadRows;
-    a.dbfc_part = owned(nblk * E_);
-    a.head_part = owned(nblk * 4);
+    a.dbfc_part = zeros_ptr<float>(nblk * E_, torch::kFloat32);
+    a.head_part = zeros_ptr<float>(nblk * 4, torch::kFloat32);
     a.prof = nullptr;
     const size_t lds = eh_tr_head_lds(a.Hin2, a.H, a.E, a.C, mode);
     TORCH_CHECK(lds <= 160 * 1024 - 64, "TreePlan: head tile does not fit in LDS (", lds, " bytes)");
@@ -543,9 +487,7 @@ class TreePlan {
     plan_splits(p, dA != nullptr);
     const int64_t S = p.S;
     // split-K partials are owned by the plan (their size follows its split plan)
-    torch::Tensor t = torch::empty({S * P * Q}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    owned_.push_back(t);
-    p.part = t.data_ptr<float>();
+    p.part = empty(S * P * Q, torch::kFloat32).data_ptr<float>();
     p.G = G;
     p.X = X;
     if (dA) {
@@ -659,9 +601,9 @@ class TreePlan {
 // routes it through the tree and the ReLU bits inside the split-K dW kernel and reduces
 // the partials into the fp32 gradient of W0.  The rest of the tower (last conv, fc, loss)
 // is ordinary torch on [R][2H0] rows (euler_amd/models/sage_tower.py).
-class TowerPlan {
+class TowerPlan : private PlanDict {
  public:
-  explicit TowerPlan(py::dict d) : d_(d) {
+  explicit TowerPlan(py::dict d) : PlanDict(d, "TowerPlan") {
     R_ = geti("R");
     F1_ = geti("F1");
     F2_ = geti("F2");
@@ -669,40 +611,14 @@ class TowerPlan {
     D_ = geti("D");
     H_ = geti("H");
     self_ = geti("include_self");
-    dev_ = T("rng").device();
-    TORCH_CHECK(dev_.is_cuda(), "TowerPlan: tensors must be on the GPU");
     TORCH_CHECK(R_ > 0 && R_ % 32 == 0, "TowerPlan: roots must be a positive multiple of 32");
     TORCH_CHECK(logP_ >= 4 && (1 << logP_) > F1_ && F1_ >= 1 && F2_ >= 1, "TowerPlan: slot group too small");
     TORCH_CHECK(D_ % 16 == 0 && H_ % 64 == 0, "TowerPlan: padded dims (D % 16, H % 64)");
     M_ = R_ << logP_;
-    // graph + tree
-    torch::Tensor indptr = T("indptr"), rng = T("rng"), nbr = T("nbr"), cumw = T("cumw"), prob = T("node_prob");
-    need(indptr, torch::kInt64, -1, "indptr");
-    need(rng, torch::kInt64, 2, "rng");
-    const int64_t nt = geti("num_types");
-    TORCH_CHECK(nt >= 1 && nt <= 32 && (indptr.numel() - 1) % nt == 0, "TowerPlan: indptr must be [N*T+1]");
-    g_.indptr = indptr.data_ptr<int64_t>();
-    g_.num_types = static_cast<int32_t>(nt);
-    g_.num_rows = (indptr.numel() - 1) / nt;
-    need(nbr, torch::kInt32, -1, "nbr");
-    need(cumw, torch::kFloat32, nbr.numel(), "cumw");
-    g_.nbr = nbr.data_ptr<int32_t>();
-    g_.cumw = cumw.data_ptr<float>();
-    need(prob, torch::kFloat32, -1, "node_prob");
-    g_.pop = prob.numel();
-    g_.prob = prob.data_ptr<float>();
-    g_.alias = ptr<int32_t>("node_alias", torch::kInt32, g_.pop);
-    // candidate -> row map of the root sampler (node-type subset); used when the roots are
-    // drawn in the sampler (PairPlan), not when they are given
-    g_.root_rows = has("root_rows") ? ptr<int32_t>("root_rows", torch::kInt32, g_.pop) : nullptr;
-    tree_.rng = rng.data_ptr<int64_t>();
-    tree_.root_in = ptr<int32_t>("roots_in", torch::kInt32, R_);
-    tree_.F1 = static_cast<int32_t>(F1_);
-    tree_.F2 = 0;
-    tree_.logP1 = static_cast<int32_t>(logP_);
-    tree_.logP2 = 0;
-    tree_.m1 = static_cast<uint32_t>(geti("mask1"));
-    tree_.m2 = 0u;
+    // graph + tree; root_rows is used when the roots are drawn in the sampler (PairPlan), not
+    // when they are given
+    fill_graph_tree(*this, g_, tree_, F1_, 0, logP_, 0, static_cast<uint32_t>(geti("mask1")), 0u);
+    tree_.root_in = i32("roots_in", R_);
     // sampler: level-1 slots (hop 1 of each root) and their F2 leaves
     sample_.g = g_;
     sample_.tr = tree_;
@@ -716,10 +632,8 @@ class TowerPlan {
     sample_.leaf = ptr<int32_t>("leaf", torch::kInt32, M_ * F2_);
     // layer 0 (mode 0)
     torch::Tensor x = T("features");
+    feat_fp32_ = !need_bf16_or_f32(x, -1, "features");
     TORCH_CHECK(x.dim() == 2 && x.size(1) == D_ && x.size(0) == g_.num_rows, "features must be [N, D]");
-    TORCH_CHECK(x.scalar_type() == torch::kBFloat16 || x.scalar_type() == torch::kFloat32, "features bf16 / fp32");
-    need(x, x.scalar_type(), -1, "features");
-    feat_fp32_ = x.scalar_type() == torch::kFloat32;
     TrFwdArgs& a = fwd_;
     a.x = x.data_ptr();
     a.D = static_cast<int32_t>(D_);
@@ -733,7 +647,7 @@ class TowerPlan {
     a.roots_cur = owned_i32(R_);
     a.B = static_cast<int32_t>(R_);
     a.step = nullptr;
-    a.rng = rng.data_ptr<int64_t>();
+    a.rng = ptr<int64_t>("rng", torch::kInt64, 2);
     a.W = ptr<uint16_t>("W0_sh", torch::kBFloat16, H_ * 2 * D_);
     a.H = static_cast<int32_t>(H_);
     a.a_kt = ptr<uint16_t>("A0_kt", torch::kBFloat16, M_ * 2 * D_);
@@ -757,8 +671,7 @@ class TowerPlan {
     if (S > (p.MB + 7) / 8 * 8) S = (p.MB + 7) / 8 * 8;
     p.kps = static_cast<int32_t>((p.MB + S - 1) / S);
     p.S = static_cast<int32_t>(S);
-    part_ = torch::empty({S * p.P * p.Q}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    p.part = part_.data_ptr<float>();
+    p.part = empty(S * p.P * p.Q, torch::kFloat32).data_ptr<float>();
     p.G = nullptr;
     p.X = a.a_kt;
     p.route = 1;
@@ -786,10 +699,8 @@ class TowerPlan {
     sg.shT = nullptr;
     o.nseg = 1;
     o.nblk = tr_seg_prepare(sg);
-    dummy_ = torch::zeros({8}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    step_ = torch::zeros({1}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
-    o.step = step_.data_ptr<int64_t>();
-    o.head_part = o.loss_acc = o.loss_out = dummy_.data_ptr<float>();
+    o.step = zeros_ptr<int64_t>(1, torch::kInt64);
+    o.head_part = o.loss_acc = o.loss_out = zeros_ptr<float>(8, torch::kFloat32);
     o.nhead = 0;
     o.counts = nullptr;
     o.nsample = 0;
@@ -798,16 +709,16 @@ class TowerPlan {
 
   // refresh the bf16 fm shadow of W0 from the fp32 master (call after each update)
   void shadow() {
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_opt(&opt_, 3, stream()), "tower shadow");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_opt(&opt_, 3, cur_stream()), "tower shadow");
   }
   void sample() {
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_sample(&sample_, stream()), "tower sample");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_sample(&sample_, cur_stream()), "tower sample");
   }
   void fwd() {
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_fwd(&fwd_, 0, feat_fp32_, bm_, stream()), "tower fwd");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_fwd(&fwd_, 0, feat_fp32_, bm_, cur_stream()), "tower fwd");
   }
   // internals for PairPlan (the fused pair step reuses this tower's sampler / forward /
   // routed dW description)
@@ -819,58 +730,29 @@ class TowerPlan {
   int64_t R() const { return R_; }
   int64_t H() const { return H_; }
   int64_t D() const { return D_; }
-  c10::Device device() const { return dev_; }
+  using PlanDict::device;
 
   // dA1 (the plan's buffer) -> gW0 (the plan's buffer)
   void bwd() {
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TrDwLaunch L{};
     L.route[0] = prob_;
     L.nroute = 1;
-    ok(eh_tr_dw(&L, stream()), "tower dw");
-    ok(eh_tr_opt(&opt_, 0, stream()), "tower reduce");
+    tree_ok(eh_tr_dw(&L, cur_stream()), "tower dw");
+    tree_ok(eh_tr_opt(&opt_, 0, cur_stream()), "tower reduce");
   }
 
  private:
-  py::dict d_;
   int64_t R_, F1_, F2_, logP_, D_, H_, self_, M_;
   int feat_fp32_ = 0, bm_ = 32;
-  c10::Device dev_{c10::kCPU};
   TrGraph g_{};
   TrTree tree_{};
   TrSampleArgs sample_{};
   TrFwdArgs fwd_{};
   TrDwProb prob_{};
   TrOptArgs opt_{};
-  torch::Tensor part_, dummy_, step_;
-  std::vector<torch::Tensor> owned_;
 
-  bool has(const char* k) const { return d_.contains(k) && !d_[k].is_none(); }
-  int64_t geti(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "TowerPlan: missing '", k, "'");
-    return d_[k].cast<int64_t>();
-  }
-  torch::Tensor T(const char* k) const {
-    TORCH_CHECK(has(k), "TowerPlan: missing tensor '", k, "'");
-    return d_[k].cast<torch::Tensor>();
-  }
-  void need(const torch::Tensor& t, c10::ScalarType st, int64_t numel, const std::string& name) const {
-    TORCH_CHECK(t.is_cuda() && t.device() == dev_, name, " must be on the tower's GPU");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-    TORCH_CHECK(t.scalar_type() == st, name, " has the wrong dtype");
-    if (numel >= 0) TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(), " elements, expected ", numel);
-  }
-  template <typename P>
-  P* ptr(const char* k, c10::ScalarType st, int64_t numel) {
-    torch::Tensor t = T(k);
-    need(t, st, numel, k);
-    return reinterpret_cast<P*>(t.data_ptr());
-  }
-  int32_t* owned_i32(int64_t n) {
-    torch::Tensor t = torch::full({n}, -1, torch::TensorOptions().dtype(torch::kInt32).device(dev_));
-    owned_.push_back(t);
-    return t.data_ptr<int32_t>();
-  }
+  int32_t* owned_i32(int64_t n) { return full(n, -1, torch::kInt32).data_ptr<int32_t>(); }
 };
 
 // The fused unsupervised GraphSAGE step (models/sage_tower.py, fused mode): both towers'
@@ -881,9 +763,9 @@ class TowerPlan {
 // (both routed W0 problems + W1 / Wfc of both towers) and ONE optimizer launch over the
 // flat parameters (split-K reduce, Adam / Adagrad / SGD / momentum, bf16 shadows, loss and
 // reciprocal-rank hand-off): 7 launches per step.
-class PairPlan {
+class PairPlan : private PlanDict {
  public:
-  PairPlan(const TowerPlan& s, const TowerPlan& c, py::dict d) : d_(d), dev_(s.device()) {
+  PairPlan(const TowerPlan& s, const TowerPlan& c, py::dict d) : PlanDict(d, "PairPlan", s.device()) {
     B_ = geti("B");
     K_ = geti("K");
     H0_ = s.H();
@@ -919,8 +801,7 @@ class PairPlan {
     fc_.roots_in = sc_.roots;
     fs_.step = step_.data_ptr<int64_t>();
     fc_.step = nullptr;
-    rng_dummy_ = torch::zeros({2}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
-    fc_.rng = rng_dummy_.data_ptr<int64_t>();
+    fc_.rng = zeros_ptr<int64_t>(2, torch::kInt64);
     // head
     nblk_ = B_ / 16;
     TrPairHeadArgs& h = head_;
@@ -930,7 +811,7 @@ class PairPlan {
     h.H1 = static_cast<int32_t>(H1_);
     h.E = static_cast<int32_t>(E_);
     h.inv_n = 1.f / static_cast<float>(B_ * (1 + K_));
-    h.head_part = owned(nblk_ * 4);
+    h.head_part = zeros_ptr<float>(nblk_ * 4, torch::kFloat32);
     tower(h.s, s, "s");
     tower(h.c, c, "c");
     // dW: routed W0 of both towers + W1 / Wfc of both towers
@@ -950,7 +831,7 @@ class PairPlan {
     TrOptArgs& o = opt_;
     torch::Tensor flat = T("flat");
     need(flat, torch::kFloat32, -1, "flat");
-    std::vector<int64_t> off = d_["offsets"].cast<std::vector<int64_t>>();
+    std::vector<int64_t> off = getv("offsets");
     // the flat buffers may end in padding (parallel/flat.py pads to a multiple of 8)
     TORCH_CHECK(off.size() == 9 && off.back() <= flat.numel(), "PairPlan: offsets = 8 segments + end");
     o.n = off.back();
@@ -994,30 +875,30 @@ class PairPlan {
   }
 
   void sample() {
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_sample(&ss_, stream()), "pair sample (source)");
-    ok(eh_tr_sample(&sc_, stream()), "pair sample (context)");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_sample(&ss_, cur_stream()), "pair sample (source)");
+    tree_ok(eh_tr_sample(&sc_, cur_stream()), "pair sample (context)");
   }
   void fwd() {
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_fwd(&fs_, 0, fpx_, bm_s_, stream()), "pair fwd (source)");
-    ok(eh_tr_fwd(&fc_, 0, fpx_, bm_c_, stream()), "pair fwd (context)");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_fwd(&fs_, 0, fpx_, bm_s_, cur_stream()), "pair fwd (source)");
+    tree_ok(eh_tr_fwd(&fc_, 0, fpx_, bm_c_, cur_stream()), "pair fwd (context)");
   }
   void head() {
-    const c10::DeviceGuard g(dev_);
-    ok(eh_tr_pair_head(&head_, stream()), "pair head");
+    const c10::DeviceGuard g(device());
+    tree_ok(eh_tr_pair_head(&head_, cur_stream()), "pair head");
   }
   void dw() {
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TrDwLaunch L = L_;
-    ok(eh_tr_dw(&L, stream()), "pair dw");
+    tree_ok(eh_tr_dw(&L, cur_stream()), "pair dw");
   }
   // 0: split-K reduce into the flat gradient; 1: optimizer from it (scaled); 2: both; 3: shadows
   void opt(int mode, double grad_scale) {
-    const c10::DeviceGuard g(dev_);
+    const c10::DeviceGuard g(device());
     TrOptArgs a = opt_;
     a.grad_scale = static_cast<float>(grad_scale);
-    ok(eh_tr_opt(&a, mode, stream()), "pair opt");
+    tree_ok(eh_tr_opt(&a, mode, cur_stream()), "pair opt");
   }
   void set_lr(double lr) { opt_.lr = static_cast<float>(lr); }
   void set_grad(torch::Tensor g) {
@@ -1028,8 +909,6 @@ class PairPlan {
   }
 
  private:
-  py::dict d_;
-  c10::Device dev_;
   int64_t B_, K_, H0_, H1_, E_, nblk_;
   int fpx_ = 0, bm_s_ = 32, bm_c_ = 32;
   TrSampleArgs ss_{}, sc_{};
@@ -1038,8 +917,7 @@ class PairPlan {
   TrDwLaunch L_{};
   int plain_[4] = {0, 0, 0, 0};
   TrOptArgs opt_{};
-  torch::Tensor step_, rng_dummy_, grad_keep_;
-  std::vector<torch::Tensor> owned_;
+  torch::Tensor step_, grad_keep_;
 
   void tower(TrPairTower& t, const TowerPlan& tp, const std::string& x) {
     const int64_t R = tp.R();
@@ -1049,12 +927,12 @@ class PairPlan {
     t.Wfc = bf(("Wfc_sh_" + x).c_str(), E_ * H1_);
     t.WfcT = bf(("Wfc_shT_" + x).c_str(), E_ * H1_);
     t.bfc = ptr<float>(("bfc_" + x).c_str(), torch::kFloat32, E_);
-    t.A1_kt = owned_bf16(R * 2 * H0_);
-    t.h_kt = owned_bf16(R * H1_);
-    t.de_kt = owned_bf16(R * E_);
-    t.g_kt = owned_bf16(R * H1_);
+    t.A1_kt = zeros_ptr<uint16_t>(R * 2 * H0_, torch::kBFloat16);
+    t.h_kt = zeros_ptr<uint16_t>(R * H1_, torch::kBFloat16);
+    t.de_kt = zeros_ptr<uint16_t>(R * E_, torch::kBFloat16);
+    t.g_kt = zeros_ptr<uint16_t>(R * H1_, torch::kBFloat16);
     t.dA1 = const_cast<float*>(tp.prob().dA);
-    t.dbfc_part = owned(nblk_ * E_);
+    t.dbfc_part = zeros_ptr<float>(nblk_ * E_, torch::kFloat32);
   }
 
   // stored-G dW problem: ~512 workgroups of 64 x 64 tiles, >= 4 k-blocks per split
@@ -1071,7 +949,7 @@ class PairPlan {
     kps = std::min<int64_t>(kps, p.MB);
     p.kps = static_cast<int32_t>(kps);
     p.S = static_cast<int32_t>((p.MB + kps - 1) / kps);
-    p.part = owned(static_cast<int64_t>(p.S) * P * Q);
+    p.part = zeros_ptr<float>(static_cast<int64_t>(p.S) * P * Q, torch::kFloat32);
     p.G = G;
     p.X = X;
     TORCH_CHECK(L_.plain.n < kTrMaxProbs, "PairPlan: too many dW problems");
@@ -1095,40 +973,6 @@ class PairPlan {
     if (cols > 0)
       TORCH_CHECK(rows % 8 == 0 && cols % 32 == 0, "PairPlan: weight segments need rows % 8, cols % 32");
     blk += tr_seg_prepare(g);
-  }
-
-  bool has(const char* k) const { return d_.contains(k) && !d_[k].is_none(); }
-  int64_t geti(const char* k) const {
-    TORCH_CHECK(d_.contains(k), "PairPlan: missing '", k, "'");
-    return d_[k].cast<int64_t>();
-  }
-  double getf(const char* k) const { return d_[k].cast<double>(); }
-  torch::Tensor T(const char* k) const {
-    TORCH_CHECK(has(k), "PairPlan: missing tensor '", k, "'");
-    return d_[k].cast<torch::Tensor>();
-  }
-  void need(const torch::Tensor& t, c10::ScalarType st, int64_t numel, const std::string& name) const {
-    TORCH_CHECK(t.is_cuda() && t.device() == dev_, name, " must be on the plan's GPU");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-    TORCH_CHECK(t.scalar_type() == st, name, " has the wrong dtype");
-    if (numel >= 0) TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(), " elements, expected ", numel);
-  }
-  template <typename P>
-  P* ptr(const char* k, c10::ScalarType st, int64_t numel) {
-    torch::Tensor t = T(k);
-    need(t, st, numel, k);
-    return reinterpret_cast<P*>(t.data_ptr());
-  }
-  uint16_t* bf(const char* k, int64_t numel) { return ptr<uint16_t>(k, torch::kBFloat16, numel); }
-  float* owned(int64_t n) {
-    torch::Tensor t = torch::zeros({n}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    owned_.push_back(t);
-    return t.data_ptr<float>();
-  }
-  uint16_t* owned_bf16(int64_t n) {
-    torch::Tensor t = torch::zeros({n}, torch::TensorOptions().dtype(torch::kBFloat16).device(dev_));
-    owned_.push_back(t);
-    return reinterpret_cast<uint16_t*>(t.data_ptr());
   }
 };
 

@@ -1,29 +1,12 @@
-// torch binding of the sharded random walk's hop kernels (walk_shard.hip).  Host-only,
-// same rules as binding.cpp: every operand is validated (dtype, device, contiguity and the
-// element counts the grids assume) before a launch; launches go to torch's current HIP
+// torch binding of the sharded random walk's hop kernels (walk_shard.hip).  Host-only;
+// operands go through binding_util.h (rules R1-R3 there); launches go to torch's current HIP
 // stream, so a walk records into a hipGraph.
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-
+#include "hip/binding_util.h"
 #include "hip/launchers.h"
 
-namespace py = pybind11;
+using namespace euler_bind;
 
 namespace {
-
-hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
-
-void ok(hipError_t e, const char* what) {
-  TORCH_CHECK(e == hipSuccess, "euler_amd HIP kernel '", what, "' failed: ", hipGetErrorString(e));
-}
-
-void typed(const torch::Tensor& t, c10::ScalarType st, const char* name, const torch::Tensor& like) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous GPU tensor");
-  TORCH_CHECK(t.scalar_type() == st, name, " has dtype ", t.scalar_type(), ", expected ", st);
-  TORCH_CHECK(t.device() == like.device(), name, " is on another device");
-}
 
 // the packed request space: R a multiple of W that covers the rows, and every key
 // (W * n tickets) * R below 2^62
@@ -37,16 +20,17 @@ void check_keys(int64_t n, int64_t num_rows, int64_t R, int64_t W, int64_t ticke
 // out [n, cols] int32 gets column 0 = starts; returns the hop-0 request keys [n] int64
 torch::Tensor walk_keys(torch::Tensor starts, torch::Tensor out, int64_t num_rows, int64_t R, int64_t W,
                         int64_t ticket0) {
-  typed(starts, torch::kInt32, "starts", starts);
-  typed(out, torch::kInt32, "out", starts);
+  const Operands c("walk_keys", starts, "starts");
+  c.i32(starts, "starts");
+  c.i32(out, "out");
   const int64_t n = starts.numel();
   TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) >= 1, "out must be [n, walk_len + 1]");
   check_keys(n, num_rows, R, W, ticket0);
-  const c10::DeviceGuard g(starts.device());
+  const auto g = c.guard();
   auto keys = torch::empty({n}, starts.options().dtype(torch::kInt64));
-  ok(eh_walk_keys(starts.data_ptr<int32_t>(), n, num_rows, R, ticket0, out.size(1), out.data_ptr<int32_t>(),
-                  keys.data_ptr<int64_t>(), stream()),
-     "walk_keys");
+  launch_ok(eh_walk_keys(starts.data_ptr<int32_t>(), n, num_rows, R, ticket0, out.size(1), out.data_ptr<int32_t>(),
+                         keys.data_ptr<int64_t>(), cur_stream()),
+            "walk_keys");
   return keys;
 }
 
@@ -54,11 +38,12 @@ torch::Tensor walk_keys(torch::Tensor starts, torch::Tensor out, int64_t num_row
 torch::Tensor walk_step_owner(torch::Tensor req, int64_t R, int64_t W, torch::Tensor indptr, torch::Tensor nbr,
                               torch::Tensor cumw, int64_t local_rows, int64_t num_types, int64_t mask, int64_t hop,
                               torch::Tensor rng, int64_t stream_id) {
-  typed(req, torch::kInt64, "req", req);
-  typed(indptr, torch::kInt64, "indptr", req);
-  typed(nbr, torch::kInt32, "nbr", req);
-  typed(cumw, torch::kFloat32, "cumw", req);
-  typed(rng, torch::kInt64, "rng_state", req);
+  const Operands c("walk_step_owner", req, "req");
+  c.i64(req, "req");
+  c.i64(indptr, "indptr");
+  c.i32(nbr, "nbr");
+  c.f32(cumw, "cumw");
+  c.i64(rng, "rng_state");
   TORCH_CHECK(rng.numel() == 2, "rng_state must have 2 elements");
   TORCH_CHECK(num_types >= 1 && num_types <= 32, "num_types must be in [1, 32]");
   TORCH_CHECK(local_rows >= 0 && indptr.numel() == local_rows * num_types + 1, "indptr size mismatch: ",
@@ -67,33 +52,34 @@ torch::Tensor walk_step_owner(torch::Tensor req, int64_t R, int64_t W, torch::Te
   TORCH_CHECK(W >= 1 && W <= 63 && R >= 1 && R % W == 0, "walk: R must be a multiple of W (1..63)");
   // every row a key can name is below R, so its local row is below R / W
   TORCH_CHECK(hop >= 0 && hop < 1024, "walk: at most 1024 hops");
-  const c10::DeviceGuard g(req.device());
+  const auto g = c.guard();
   auto ans = torch::empty({req.numel()}, req.options().dtype(torch::kInt32));
-  ok(eh_walk_step_owner(req.data_ptr<int64_t>(), req.numel(), R, static_cast<int>(W), indptr.data_ptr<int64_t>(),
-                        nbr.data_ptr<int32_t>(), cumw.data_ptr<float>(), local_rows, static_cast<int>(num_types),
-                        static_cast<uint32_t>(mask), static_cast<int>(hop), rng.data_ptr<int64_t>(),
-                        static_cast<uint64_t>(stream_id), ans.data_ptr<int32_t>(), stream()),
-     "walk_step_owner");
+  launch_ok(eh_walk_step_owner(req.data_ptr<int64_t>(), req.numel(), R, static_cast<int>(W), indptr.data_ptr<int64_t>(),
+                               nbr.data_ptr<int32_t>(), cumw.data_ptr<float>(), local_rows, static_cast<int>(num_types),
+                               static_cast<uint32_t>(mask), static_cast<int>(hop), rng.data_ptr<int64_t>(),
+                               static_cast<uint64_t>(stream_id), ans.data_ptr<int32_t>(), cur_stream()),
+            "walk_step_owner");
   return ans;
 }
 
 // column `col` of out from the returned answers; returns the next hop's request keys [n]
 torch::Tensor walk_unroute(torch::Tensor back, torch::Tensor pos, torch::Tensor out, int64_t col,
                            int64_t default_row, int64_t num_rows, int64_t R, int64_t W, int64_t ticket0) {
-  typed(back, torch::kInt32, "back", back);
-  typed(pos, torch::kInt64, "pos", back);
-  typed(out, torch::kInt32, "out", back);
+  const Operands c("walk_unroute", back, "back");
+  c.i32(back, "back");
+  c.i64(pos, "pos");
+  c.i32(out, "out");
   const int64_t n = pos.numel();
   TORCH_CHECK(out.dim() == 2 && out.size(0) == n, "out must be [n, walk_len + 1]");
   TORCH_CHECK(col >= 1 && col < out.size(1), "walk_unroute: column out of range");
   TORCH_CHECK(default_row >= INT32_MIN && default_row <= INT32_MAX, "default row must fit int32");
   check_keys(n, num_rows, R, W, ticket0);
-  const c10::DeviceGuard g(back.device());
+  const auto g = c.guard();
   auto keys = torch::empty({n}, pos.options());
-  ok(eh_walk_unroute(back.data_ptr<int32_t>(), back.numel(), pos.data_ptr<int64_t>(), n,
-                     static_cast<int32_t>(default_row), num_rows, R, ticket0, out.size(1), col,
-                     out.data_ptr<int32_t>(), keys.data_ptr<int64_t>(), stream()),
-     "walk_unroute");
+  launch_ok(eh_walk_unroute(back.data_ptr<int32_t>(), back.numel(), pos.data_ptr<int64_t>(), n,
+                            static_cast<int32_t>(default_row), num_rows, R, ticket0, out.size(1), col,
+                            out.data_ptr<int32_t>(), keys.data_ptr<int64_t>(), cur_stream()),
+            "walk_unroute");
   return keys;
 }
 

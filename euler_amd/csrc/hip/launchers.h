@@ -1,4 +1,4 @@
-// C ABI of the gfx950 kernel launchers (implemented in *.hip, used by binding.cpp).
+// C ABI of the gfx950 kernel launchers (implemented in *.hip, used by the binding*.cpp files).
 // Every launcher is asynchronous on the given stream, allocates nothing and never
 // synchronises, so callers may capture it into a hipGraph.
 #pragma once

@@ -237,6 +237,7 @@ class GcnTrainer(CapturedTrainer):
              "loss_out": self.loss_out, "counts": self.counts, "layer_draws": self.layer_draws}
         if L == 2:
             d.update({"H1": int(w[1].shape[0]), "w1": w[1].detach(), "g_w1": w[1].grad})
+        self._buf = d  # the plan's dict, kept like SageTrainer's
         self.plan = hip().GcnPlan(d)
         self.flow.on_clear = self.plan.reset_counters
         self._plan_caps = list(self.flow.caps)
