@@ -69,6 +69,17 @@ void fill_graph_tree(PlanDict& pd, TrGraph& g, TrTree& tr, int64_t F1, int64_t F
   tr.m2 = m2;
 }
 
+// split plan of a stored-G dW problem from the keys every plan shares: dw_target_wg (512),
+// dw_min_kps (4), dw_fold (1; 0 = every slab goes through `part`)
+void plan_stored(const PlanDict& pd, TrDwProb& p) {
+  const int64_t target = pd.has("dw_target_wg") ? pd.geti("dw_target_wg") : 512;
+  const int64_t minkps = pd.has("dw_min_kps") ? pd.geti("dw_min_kps") : 4;
+  const int64_t fold = pd.has("dw_fold") ? pd.geti("dw_fold") : 1;
+  TORCH_CHECK(target >= 1 && minkps >= 1 && (fold == 0 || fold == 1), pd.name(),
+              ": dw_target_wg / dw_min_kps must be positive, dw_fold 0 or 1");
+  tr_plan_stored(p, target, minkps, fold == 1);
+}
+
 class TreePlan : private PlanDict {
  public:
   explicit TreePlan(py::dict d) : PlanDict(d, "TreePlan") {
@@ -264,6 +275,12 @@ class TreePlan : private PlanDict {
     std::vector<int64_t> s;
     for (const auto& p : probs_) s.push_back(p.S);
     return s;
+  }
+  // slabs each problem sums inside its blocks (0: none, its S slabs go through `part`)
+  std::vector<int64_t> folds() const {
+    std::vector<int64_t> f;
+    for (const auto& p : probs_) f.push_back(p.F);
+    return f;
   }
 
  private:
@@ -468,14 +485,7 @@ class TreePlan : private PlanDict {
       p.S = static_cast<int32_t>(S);  // >= ceil(MB / kps); trailing splits may be empty
       return;
     }
-    const int64_t tiles = ((p.P + 63) / 64) * ((p.Q + 63) / 64);
-    const int64_t target = has("dw_target_wg") ? geti("dw_target_wg") : 512;
-    const int64_t minkps = has("dw_min_kps") ? geti("dw_min_kps") : 4;
-    int64_t kps = (MB * tiles + target - 1) / target;
-    if (kps < minkps) kps = minkps;
-    if (kps > MB) kps = MB;
-    p.kps = static_cast<int32_t>(kps);
-    p.S = static_cast<int32_t>((MB + kps - 1) / kps);
+    plan_stored(*this, p);
   }
 
   void add_prob(const std::string& /*name*/, int64_t P, int64_t Q, int64_t M, const uint16_t* G, const uint16_t* X,
@@ -907,6 +917,19 @@ class PairPlan : private PlanDict {
     grad_keep_ = g;
     opt_.g = g.data_ptr<float>();
   }
+  // the dW launch's problems, routed first: slabs the optimizer sums / slabs summed in the block
+  std::vector<int64_t> splits() const {
+    std::vector<int64_t> s;
+    for (int r = 0; r < L_.nroute; ++r) s.push_back(L_.route[r].S);
+    for (int i = 0; i < L_.plain.n; ++i) s.push_back(L_.plain.p[i].S);
+    return s;
+  }
+  std::vector<int64_t> folds() const {
+    std::vector<int64_t> f;
+    for (int r = 0; r < L_.nroute; ++r) f.push_back(L_.route[r].F);
+    for (int i = 0; i < L_.plain.n; ++i) f.push_back(L_.plain.p[i].F);
+    return f;
+  }
 
  private:
   int64_t B_, K_, H0_, H1_, E_, nblk_;
@@ -935,20 +958,14 @@ class PairPlan : private PlanDict {
     t.dbfc_part = zeros_ptr<float>(nblk_ * E_, torch::kFloat32);
   }
 
-  // stored-G dW problem: ~512 workgroups of 64 x 64 tiles, >= 4 k-blocks per split
+  // stored-G dW problem (plan_stored: the split plan TreePlan uses)
   int add_plain(int64_t P, int64_t Q, int64_t M, const uint16_t* G, const uint16_t* X) {
     TORCH_CHECK(M % 32 == 0 && P % 32 == 0 && Q % 32 == 0, "PairPlan: dW problem shapes");
     TrDwProb p{};
     p.P = static_cast<int32_t>(P);
     p.Q = static_cast<int32_t>(Q);
     p.MB = static_cast<int32_t>(M / 32);
-    const int64_t tiles = ((P + 63) / 64) * ((Q + 63) / 64);
-    const int64_t target = has("dw_target_wg") ? geti("dw_target_wg") : 512;
-    int64_t kps = (p.MB * tiles + target - 1) / target;
-    kps = std::max<int64_t>(kps, 4);
-    kps = std::min<int64_t>(kps, p.MB);
-    p.kps = static_cast<int32_t>(kps);
-    p.S = static_cast<int32_t>((p.MB + kps - 1) / kps);
+    plan_stored(*this, p);
     p.part = zeros_ptr<float>(static_cast<int64_t>(p.S) * P * Q, torch::kFloat32);
     p.G = G;
     p.X = X;
@@ -998,6 +1015,7 @@ void register_tree_ops(py::module& m) {
       .def("set_grad", &TreePlan::set_grad, py::arg("g"))
       .def("num_problems", &TreePlan::num_problems)
       .def("splits", &TreePlan::splits)
+      .def("folds", &TreePlan::folds)
       .def("problems", &TreePlan::problems, py::arg("route"));
   m.attr("tree_head_rows") = kTrHeadRows;
   py::class_<TowerPlan>(m, "TowerPlan")
@@ -1014,5 +1032,7 @@ void register_tree_ops(py::module& m) {
       .def("dw", &PairPlan::dw)
       .def("opt", &PairPlan::opt, py::arg("mode"), py::arg("grad_scale") = 1.0)
       .def("set_lr", &PairPlan::set_lr)
-      .def("set_grad", &PairPlan::set_grad);
+      .def("set_grad", &PairPlan::set_grad)
+      .def("splits", &PairPlan::splits)
+      .def("folds", &PairPlan::folds);
 }

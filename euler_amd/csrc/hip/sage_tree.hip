@@ -1738,14 +1738,7 @@ __device__ __forceinline__ void tr_dw_route_reg_body(const TrDwProb& pr, int b, 
 // part[s][p][q] = sum_{m in split s} G[m][p] X[m][q]; 64x64 tiles, 4 waves of 32x32,
 // k-block groups double-buffered in registers (unrolled ping-pong: no register copies)
 // ----------------------------------------------------------------------------
-__device__ __forceinline__ void tr_dw_plain_body(const TrDwProbs& probs, int b, int nwg) {
-  const int id = xcd_remap(b, nwg);
-  // constant indices only (no dynamic indexing of kernel arguments)
-  TrDwProb pr = probs.p[0];
-#pragma unroll
-  for (int i = 1; i < kTrMaxProbs; ++i)
-    if (probs.n > i && id >= probs.p[i].wg0) pr = probs.p[i];
-  const int local = id - pr.wg0;
+__device__ __forceinline__ void tr_dw_plain_body(const TrDwProb& pr, int local) {
   const int s = local / pr.ntiles;
   const int tile = local - s * pr.ntiles;
   const int tp = tile / pr.tiles_q, tq = tile - (tile / pr.tiles_q) * pr.tiles_q;
@@ -1756,7 +1749,7 @@ __device__ __forceinline__ void tr_dw_plain_body(const TrDwProbs& probs, int b, 
   const int mb0 = s * pr.kps;
   const int mb1 = (mb0 + pr.kps) < pr.MB ? (mb0 + pr.kps) : pr.MB;
   const int64_t P = pr.P, Q = pr.Q;
-  if (p0 >= P || q0 >= Q) return;  // 32-wide edge of a 64-wide tile; no barriers in this kernel
+  if (p0 >= P || q0 >= Q) return;  // 32-wide edge of a 64-wide tile; no barriers in this body
   float4_t acc[2][2];
   tl_zero(acc);
   constexpr int KB = 4;
@@ -1805,6 +1798,108 @@ __device__ __forceinline__ void tr_dw_plain_body(const TrDwProbs& probs, int b, 
         out[(p0 + fm * 16 + (lane >> 4) * 4 + j) * Q + q0 + fn * 16 + lr] = acc[fm][fn][j];
 }
 
+// ----------------------------------------------------------------------------
+// tr_dw_fold: a stored-G problem whose F split-K slabs are summed inside the block.  One
+// workgroup owns one 32x32 tile over all of K; wave w computes the slabs w, w + 4, ... one
+// after the other, each exactly as tr_dw_plain_body computes it (accumulators zeroed per
+// slab, the same MFMAs in k order, the same clamped loads), and parks each finished slab in
+// LDS slot s.  After the barrier the 256 threads add the slots in slab order, which is the
+// sum tr_opt made of the slabs in `part`: the same adds on the same operands, so the same
+// bits, and the slabs never travel through memory.  The k-block groups of all the wave's slabs
+// form one ping-pong sequence: the next group's loads (the next slab's, at a slab's end) are
+// issued before this group's MFMAs.
+// Slot layout [32 rows][32 cols] fp32 with the 16-column halves swapped in rows with bit 2 set
+// (tr_fold_off).  An accumulator store (ds_write_b32, 32-lane groups) writes 16 columns of
+// rows r and r + 4: the swap puts them on the two halves of the 32 banks.  The fold reads 16 B
+// per thread, 8 threads per row; a 16-lane group of ds_read_b128 covers 4 rows x 16 columns
+// that lie on 64 distinct banks with or without the swap (bit 2 is equal within 4 rows).
+// ----------------------------------------------------------------------------
+static_assert(sizeof(RouteLds) >= kTrFoldLds, "the fold's slots alias the routed body's G tile");
+__device__ __forceinline__ int tr_fold_off(int row, int col) { return row * 32 + (col ^ ((row & 4) << 2)); }
+
+__device__ __forceinline__ void tr_dw_fold_body(const TrDwProb& pr, int tile, float* slots) {
+  const int tp = tile / pr.tiles_q, tq = tile - tp * pr.tiles_q;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int lr = lane & 15, lk = (lane >> 4) * 8;
+  const int p0 = tp * 32, q0 = tq * 32;
+  const int64_t P = pr.P, Q = pr.Q;
+  const int F = pr.F, MB = pr.MB, kps = pr.kps;
+  constexpr int KB = 4;
+  struct Grp {
+    uint4_t a[KB][2], b[KB][2];
+  };
+  // k-blocks [m0, m1) of slab sl (empty past MB: that slab is all zeros)
+  auto slab = [&](int sl, int& m0, int& m1) {
+    m0 = sl * kps < MB ? sl * kps : MB;
+    m1 = (m0 + kps) < MB ? (m0 + kps) : MB;
+  };
+  auto load = [&](Grp& g, int sl, int mbs, int mb1) {
+    if (sl >= F || mbs >= mb1) return;  // uniform per wave
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      const int64_t mb = (mbs + u) < mb1 ? (mbs + u) : (mb1 - 1);
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        g.a[u][f] = *reinterpret_cast<const uint4_t*>(pr.G + ((mb * P + p0 + f * 16 + lr) * 32 + lk));
+        g.b[u][f] = *reinterpret_cast<const uint4_t*>(pr.X + ((mb * Q + q0 + f * 16 + lr) * 32 + lk));
+      }
+    }
+  };
+  float4_t acc[2][2];
+  tl_zero(acc);
+  auto compute = [&](const Grp& g, int mbs, int mb1) {
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      if (mbs + u >= mb1) break;  // uniform
+#pragma unroll
+      for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < 2; ++fn) acc[fm][fn] = mfma16(g.a[u][fm], g.b[u][fn], acc[fm][fn]);
+    }
+  };
+  // the wave's position: slab s, its k-blocks from mbs on, the slab's end mb1
+  int s = wave, mbs = 0, mb1 = 0;
+  // one group: the next group's loads, this group's MFMAs, and at a slab's end its tile to LDS
+  auto step = [&](const Grp& cur, Grp& nxt) -> bool {
+    int ns = s, nmbs = mbs + KB, nmb1 = mb1;
+    if (nmbs >= mb1) {
+      ns = s + 4;
+      slab(ns, nmbs, nmb1);
+    }
+    load(nxt, ns, nmbs, nmb1);
+    compute(cur, mbs, mb1);
+    if (ns != s) {
+      float* slot = slots + s * (32 * 32);
+#pragma unroll
+      for (int fm = 0; fm < 2; ++fm)
+#pragma unroll
+        for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) slot[tr_fold_off(fm * 16 + (lane >> 4) * 4 + j, fn * 16 + lr)] = acc[fm][fn][j];
+      tl_zero(acc);
+    }
+    s = ns;
+    mbs = nmbs;
+    mb1 = nmb1;
+    return s < F;
+  };
+  if (s < F) {
+    slab(s, mbs, mb1);
+    Grp A, B;
+    load(A, s, mbs, mb1);
+    while (step(A, B) && step(B, A)) {
+    }
+  }
+  __syncthreads();
+  // thread = (row, 4 columns): the slots in slab order, then one whole 128-byte line of the
+  // tile per 8 lanes
+  const int row = tid >> 3, c4 = (tid & 7) * 4;
+  const float* src = slots + tr_fold_off(row, c4);
+  float4_t g = {0.f, 0.f, 0.f, 0.f};
+  for (int sl = 0; sl < F; ++sl) g += *reinterpret_cast<const float4_t*>(src + sl * (32 * 32));
+  *reinterpret_cast<float4_t*>(pr.part + (p0 + row) * Q + q0 + c4) = g;
+}
+
 __global__ __launch_bounds__(256, 2) void tr_dw_all_kernel(TrDwLaunch a) {
   __shared__ __attribute__((aligned(16))) RouteLds gs;
   __shared__ uint4_t lut[256];
@@ -1821,7 +1916,14 @@ __global__ __launch_bounds__(256, 2) void tr_dw_all_kernel(TrDwLaunch a) {
     else tr_dw_route_body(a.route[1], b - a.rwg[1], gs, lut, nullptr);
   } else {
     const int r = a.rwg[a.nroute];
-    tr_dw_plain_body(a.plain, b - r, static_cast<int>(gridDim.x) - r);
+    const int id = xcd_remap(b - r, static_cast<int>(gridDim.x) - r);
+    // constant indices only (no dynamic indexing of kernel arguments)
+    TrDwProb pr = a.plain.p[0];
+#pragma unroll
+    for (int i = 1; i < kTrMaxProbs; ++i)
+      if (a.plain.n > i && id >= a.plain.p[i].wg0) pr = a.plain.p[i];
+    if (pr.F > 0) tr_dw_fold_body(pr, id - pr.wg0, reinterpret_cast<float*>(&gs[0][0][0]));  // uniform per block
+    else tr_dw_plain_body(pr, id - pr.wg0);
   }
 }
 
@@ -1899,8 +2001,10 @@ __device__ __forceinline__ void tr_opt_tile(const TrOptArgs& a, int b, float (*t
       // flight measured slower: 9.38 vs 8.75 us, profiles/r3_headline/)
       const float* src = sg.part + (i - sg.off);
       g = 0.f;
+      // one slab (a dW problem summed in its blocks, tr_dw_fold_body): one load; uniform
+      if (sg.S == 1) g += src[0];
       // slabs sub, sub + grp, ... (grp == 1: all of them, in order)
-      for (int s0 = sub; s0 < sg.S; s0 += 16 * grp) {
+      for (int s0 = sub; sg.S > 1 && s0 < sg.S; s0 += 16 * grp) {
         float v[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
@@ -2206,6 +2310,15 @@ hipError_t eh_tr_dw(TrDwLaunch* L, hipStream_t s) {
     TrDwProb& p = pr->p[i];
     if (p.P % 32 != 0 || p.Q % 32 != 0 || p.MB < 1 || p.kps < 1) return hipErrorInvalidValue;
     if (p.route || !p.G || !p.X || !p.part) return hipErrorInvalidValue;
+    if (p.F < 0 || p.F > kTrFoldMax || p.S < 1) return hipErrorInvalidValue;
+    if (p.F > 0) {  // folded: F slabs cover K, one `part` slab, one workgroup per 32x32 tile
+      if (p.S != 1 || static_cast<int64_t>(p.F) * p.kps < p.MB) return hipErrorInvalidValue;
+      p.tiles_q = p.Q / 32;
+      p.ntiles = (p.P / 32) * p.tiles_q;
+      p.wg0 = wg;
+      wg += p.ntiles;
+      continue;
+    }
     if (static_cast<int64_t>(p.S) * p.kps < p.MB) return hipErrorInvalidValue;
     p.tiles_q = (p.Q + 63) / 64;
     p.ntiles = ((p.P + 63) / 64) * p.tiles_q;

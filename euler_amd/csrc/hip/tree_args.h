@@ -174,6 +174,9 @@ struct TrDwProb {
   const uint16_t* X;     // kt [M/32][Q][32]
   float* part;           // [S][P][Q]
   int32_t P, Q, MB, kps, S, tiles_q, ntiles, wg0;
+  int32_t F;             // stored-G problems: > 0 = the F slabs of kps k-blocks are summed inside the
+                         // block (32x32 tiles, one workgroup per tile over all of K; S == 1); 0 = S
+                         // slabs in `part`, one workgroup per 64x64 tile and slab
   const float* dA;       // route: [M >> logPg][2P]
   const uint32_t* mask;  // route: [M/32][P]
   int32_t route, logPg, Fg, include_self;
@@ -183,6 +186,24 @@ struct TrDwProbs {
   TrDwProb p[kTrMaxProbs];
   int32_t n;
 };
+// the in-block fold keeps one 32x32 fp32 tile (4 KiB) per slab in the dW launch's LDS
+constexpr int kTrFoldLds = 64 * 1024;  // == sizeof(RouteLds), the area the fold aliases
+constexpr int kTrFoldMax = kTrFoldLds / (32 * 32 * 4);
+// split-K plan of a stored-G problem (P, Q, MB set): ~target workgroups of 64x64 tiles, at
+// least min_kps 32-row k-blocks per slab.  With `fold` and at most kTrFoldMax slabs the block
+// sums them (F = the slab count, S = 1: `part` and the optimizer see one slab); more slabs
+// keep the global path (F = 0, S = the slab count).
+inline void tr_plan_stored(TrDwProb& p, int64_t target, int64_t min_kps, bool fold) {
+  const int64_t MB = p.MB;
+  const int64_t tiles = ((p.P + 63) / 64) * ((p.Q + 63) / 64);
+  int64_t kps = (MB * tiles + target - 1) / target;
+  if (kps < min_kps) kps = min_kps;
+  if (kps > MB) kps = MB;
+  const int64_t slabs = (MB + kps - 1) / kps;
+  p.kps = static_cast<int32_t>(kps);
+  p.F = fold && slabs <= kTrFoldMax ? static_cast<int32_t>(slabs) : 0;
+  p.S = p.F ? 1 : static_cast<int32_t>(slabs);
+}
 
 // flat parameter buffer segments: gradient = sum of S partials [S][n] (split-K slabs of a
 // dW problem, or the head's per-block fc-bias sums).  Weight matrices (cols > 0, rows % 8
@@ -262,7 +283,7 @@ hipError_t eh_tr_fwd(const euler_hip::TrFwdArgs* a, int mode, int feat_fp32, int
 size_t eh_tr_gather32_lds(int D, int FL);
 hipError_t eh_tr_head(const euler_hip::TrHeadArgs* a, int64_t B, hipStream_t s);
 hipError_t eh_tr_bwd(const euler_hip::TrBwdArgs* a, hipStream_t s);
-// fills S / tiles / wg0 of every problem from P, Q, MB, kps before launching
+// fills tiles / wg0 of every problem from P, Q, S, F before launching
 hipError_t eh_tr_dw(euler_hip::TrDwLaunch* p, hipStream_t s);
 // mode 0: split-K reduce into g; 1: optimizer from g; 2: both fused (single process);
 // 3: shadows only (after an external parameter write).  Modes 1/2 also run a->nsample

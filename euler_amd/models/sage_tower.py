@@ -211,6 +211,8 @@ class UnsupSageTrainer:
             d[f"Wfc_sh_{x}"] = torch.zeros(E * H1, **bf)
             d[f"Wfc_shT_{x}"] = torch.zeros(E * H1, **bf)
             d[f"bfc_{x}"] = self.params[f"{t}.bfc"]
+        if os.environ.get("EULER_AMD_DW_FOLD"):  # 0: the W1 / Wfc split-K slabs go through memory
+            d["dw_fold"] = int(os.environ["EULER_AMD_DW_FOLD"])
         self._pair_keep = d
         self.pair = hip().PairPlan(self.towers["gnn"].plan, self.towers["context_gnn"].plan, d)
         self.pair.opt(3)  # bf16 shadows of every weight

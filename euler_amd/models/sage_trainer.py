@@ -324,7 +324,7 @@ class SageTrainer:
              "lr": self.lr, "beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps,
              "weight_decay": self.wd, "opt_kind": _OPT_KIND[self.opt_name]}
         for key in ("EULER_AMD_DW_TARGET_WG", "EULER_AMD_DW_MIN_KPS", "EULER_AMD_DW_ROUTE_WG", "EULER_AMD_FWD_BM",
-                    "EULER_AMD_DW_ROUTE_IMPL"):
+                    "EULER_AMD_DW_ROUTE_IMPL", "EULER_AMD_DW_FOLD"):
             if os.environ.get(key):
                 d[key[len("EULER_AMD_"):].lower()] = int(os.environ[key])
         M_last = self.M[L - 1]

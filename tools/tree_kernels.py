@@ -59,6 +59,7 @@ def main():
     for i in range(p.num_problems()):
         res[f"dw[{i}]"] = round(timeit(lambda: p.dw([i]), args.reps), 2)
     res["dw_splits"] = p.splits()
+    res["dw_folds"] = p.folds()
     res["route_profile"] = route_profile(tr)
     tr.capture(steps=4)
     res["graph_step"] = round(timeit(lambda: tr.replay(1), args.reps), 2)
