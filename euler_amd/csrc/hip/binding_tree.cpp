@@ -80,6 +80,15 @@ void plan_stored(const PlanDict& pd, TrDwProb& p) {
   tr_plan_stored(p, target, minkps, fold == 1);
 }
 
+// body of the routed dW problems, the key every plan shares: dw_route_impl (2: the pipelined
+// stage loop; 0: build, load and multiply one after the other, the equality baseline; 1 was a
+// body that built G per wave in registers: slower than both, profiles/dw_route_pipe/README.md)
+int plan_route_impl(const PlanDict& pd) {
+  const int64_t impl = pd.has("dw_route_impl") ? pd.geti("dw_route_impl") : 2;
+  TORCH_CHECK(impl == 0 || impl == 2, pd.name(), ": dw_route_impl must be 0 or 2");
+  return static_cast<int>(impl);
+}
+
 class TreePlan : private PlanDict {
  public:
   explicit TreePlan(py::dict d) : PlanDict(d, "TreePlan") {
@@ -106,7 +115,7 @@ class TreePlan : private PlanDict {
     M_.assign(L_, 0);
     M_[0] = B_;
     for (int k = 1; k < L_; ++k) M_[k] = M_[k - 1] << logP_[k];
-    if (has("dw_route_impl")) route_impl_ = static_cast<int>(geti("dw_route_impl"));
+    route_impl_ = plan_route_impl(*this);
     fill_graph_tree(*this, graph_, tree_, L_ > 1 ? F_[1] : 0, L_ > 2 ? F_[2] : 0, L_ > 1 ? logP_[1] : 0,
                     L_ > 2 ? logP_[2] : 0, static_cast<uint32_t>(masks_[1]),
                     L_ > 2 ? static_cast<uint32_t>(masks_[2]) : 0u);
@@ -286,7 +295,7 @@ class TreePlan : private PlanDict {
  private:
   int L_, B_, D_, E_, C_, C_real_, self_;
   int feat_fp32_ = 0, bm0_ = 32, bm1_ = 32;
-  int route_impl_ = 0;  // EULER_AMD_DW_ROUTE_IMPL / plan key dw_route_impl
+  int route_impl_ = 2;  // EULER_AMD_DW_ROUTE_IMPL / plan key dw_route_impl (plan_route_impl)
   bool cached_ = false;
   std::vector<int64_t> F_, logP_, masks_, dims_, M_;
   TrGraph graph_{};
@@ -625,6 +634,7 @@ class TowerPlan : private PlanDict {
     TORCH_CHECK(logP_ >= 4 && (1 << logP_) > F1_ && F1_ >= 1 && F2_ >= 1, "TowerPlan: slot group too small");
     TORCH_CHECK(D_ % 16 == 0 && H_ % 64 == 0, "TowerPlan: padded dims (D % 16, H % 64)");
     M_ = R_ << logP_;
+    route_impl_ = plan_route_impl(*this);
     // graph + tree; root_rows is used when the roots are drawn in the sampler (PairPlan), not
     // when they are given
     fill_graph_tree(*this, g_, tree_, F1_, 0, logP_, 0, static_cast<uint32_t>(geti("mask1")), 0u);
@@ -748,13 +758,14 @@ class TowerPlan : private PlanDict {
     TrDwLaunch L{};
     L.route[0] = prob_;
     L.nroute = 1;
+    L.route_impl = route_impl_;
     tree_ok(eh_tr_dw(&L, cur_stream()), "tower dw");
     tree_ok(eh_tr_opt(&opt_, 0, cur_stream()), "tower reduce");
   }
 
  private:
   int64_t R_, F1_, F2_, logP_, D_, H_, self_, M_;
-  int feat_fp32_ = 0, bm_ = 32;
+  int feat_fp32_ = 0, bm_ = 32, route_impl_ = 2;
   TrGraph g_{};
   TrTree tree_{};
   TrSampleArgs sample_{};
@@ -828,6 +839,7 @@ class PairPlan : private PlanDict {
     L_.route[0] = s.prob();
     L_.route[1] = c.prob();
     L_.nroute = 2;
+    L_.route_impl = plan_route_impl(*this);
     L_.plain.n = 0;
     const char* tn[2] = {"s", "c"};
     const int64_t R[2] = {B_, B_ * (1 + K_)};

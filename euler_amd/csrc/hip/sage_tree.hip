@@ -1514,21 +1514,32 @@ __device__ __forceinline__ uint4_t tr_route_frag(const TrDwProb& pr, const Route
 // self slots is two 8-bit masks of j0, the ReLU bits pick rows, and `lut` (256 entries,
 // LDS) spreads an 8-bit row set into the 0xffff halves of 4 words; the values are the
 // bf16 pair of dn (resp. ds), rounded exactly like pack_bf16x8.
-__device__ __forceinline__ uint4_t tr_route_frag_lut(const TrDwProb& pr, const RouteRaw& r, int mb, int lk,
-                                                     const uint4_t* lut) {
-  const int j0 = static_cast<int>((static_cast<int64_t>(mb) * 32 + lk) & ((int64_t(1) << pr.logPg) - 1));
-  const int dF = pr.Fg - j0;
+// In two halves, so that a caller can put other work between the table reads and their use:
+// the spread row sets of the neighbour and the self slots (b8: the ReLU bits of the 8 rows,
+// dF = Fg - j0, j0 the slot of the fragment's first row within its sibling group) ...
+struct RouteSpread {
+  uint4_t n, s;
+};
+__device__ __forceinline__ RouteSpread tr_route_spread(uint32_t b8, int dF, const uint4_t* lut) {
   const uint32_t nm = dF >= 8 ? 0xffu : (dF <= 0 ? 0u : ((1u << dF) - 1u));
   const uint32_t sm = (dF >= 0 && dF < 8) ? (1u << dF) : 0u;
-  const uint32_t b8 = r.bits & 0xffu;
+  return RouteSpread{lut[b8 & nm], lut[b8 & sm]};
+}
+// ... and the values laid over them
+__device__ __forceinline__ uint4_t tr_route_combine(const TrDwProb& pr, const RouteRaw& r, const RouteSpread& m) {
   const float dn = r.dn * pr.inv;
   const float ds = r.ds + (pr.include_self ? dn : 0.f);
   const uint32_t DN = pack_bf16x2(dn, dn), DS = pack_bf16x2(ds, ds);
-  const uint4_t mN = lut[b8 & nm], mS = lut[b8 & sm];
   uint4_t out;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) out[i] = (DN & mN[i]) | (DS & mS[i]);
+  for (int i = 0; i < 4; ++i) out[i] = (DN & m.n[i]) | (DS & m.s[i]);
   return out;
+}
+
+__device__ __forceinline__ uint4_t tr_route_frag_lut(const TrDwProb& pr, const RouteRaw& r, int mb, int lk,
+                                                     const uint4_t* lut) {
+  const int j0 = static_cast<int>((static_cast<int64_t>(mb) * 32 + lk) & ((int64_t(1) << pr.logPg) - 1));
+  return tr_route_combine(pr, r, tr_route_spread(r.bits & 0xffu, pr.Fg - j0, lut));
 }
 
 // lut[b] word i = (bit 2i of b ? 0x0000ffff : 0) | (bit 2i + 1 ? 0xffff0000 : 0); one entry
@@ -1655,73 +1666,191 @@ __device__ __forceinline__ void tr_dw_route_body(const TrDwProb& pr, int b, Rout
 }
 
 // ----------------------------------------------------------------------------
-// tr_dw_route_reg: the routed dW without the LDS G tile or any barrier.  Every wave builds
-// the G^T fragments of all 64 p rows of the tile in registers (p = p0 + 16 fm + lr, rows
-// lk..lk+7 of the k-block) from the ReLU bits and the parent's dA row (4x redundant across
-// the block's waves, served by L1) and multiplies them by its own 32 X columns; k-block
-// groups of kRG double-buffered in registers like the plain body, so the next group's
-// loads are in flight behind this group's build + MFMAs.
+// tr_dw_route_pipe: tr_dw_route_body with the three phases of a stage (build the G tile, load
+// the next operands, multiply) woven into one straight-line block per stage.  Same tile, slabs,
+// block mapping, G values and LDS layout; every accumulator gets the same MFMAs in the same k
+// order from zero, so the slabs are the same bits.
+// One register ring of kRKB k-blocks, refilled in place.  In stage t, at k-block u:
+//   - the A fragments of k-block u + 1 are read from this stage's G tile (two register sets),
+//   - the G fragment of k-block u of stage t + 1 is built from r[u] and stored to the OTHER tile,
+//   - r[u] is reloaded with the raw operands of stage t + 2,
+//   - the 8 MFMAs of k-block u run on x[u],
+//   - x[u] is reloaded with the X fragments of stage t + 1.
+// So every global load has one stage of MFMAs to arrive, and a stage has no phase in which the
+// MFMA pipe only waits.  One barrier per stage.  Write after read: the stores of stage t go to
+// the tile that stage t - 1 read; a wave reaches the barrier that ends stage t - 1 only after
+// its MFMAs of that stage were issued, which wait for the fragment reads they consume, so no
+// read of that tile is pending when the first store of stage t is issued.  Read after write:
+// __syncthreads() waits for the wave's own LDS stores before the barrier, and the first read
+// of stage t + 1 comes after it.
+// A stage is branch-free (compile-time counts); the slab's last two stages take the same code
+// without the refills that have nothing to fetch, and a last stage of fewer than kRKB k-blocks
+// counts its MFMAs at run time (a missing k-block is skipped, not multiplied by zeros).
+// Addresses: one 32-bit byte offset per thread and operand, the k-block's base is uniform.
+// Waves whose 32 columns lie past Q (Q % 128 == 32 or 64) run on the tile's first columns and
+// store nothing: they build their share of G and reach every barrier.
 // ----------------------------------------------------------------------------
-constexpr int kRG = 4;
-__device__ __forceinline__ void tr_dw_route_reg_body(const TrDwProb& pr, int b, const uint4_t* lut, long long* prof) {
+template <int N>
+struct RtCount {
+  __device__ constexpr operator int() const { return N; }
+};
+
+__device__ __forceinline__ void tr_dw_route_pipe_body(const TrDwProb& pr, int b, RouteLds& gs, uint4_t* lut,
+                                                      long long* prof) {
   RT_STAMP(0);
   const int j = b >> 3;
   const int tile = j % pr.ntiles;
   const int s = (j / pr.ntiles) * 8 + (b & 7);
   const int tp = tile / pr.tiles_q, tq = tile - tp * pr.tiles_q;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int lr = lane & 15, lk = (lane >> 4) * 8;
-  const int p0 = tp * kRP;
-  const int wq = tq * kRQ + wave * 32;
-  const int64_t Q = pr.Q, P = pr.P;
-  if (wq >= Q) return;  // no barriers in this body
+  const int bpl = tid >> 2, blk = (tid & 3) * 8;  // builder: column p = bpl, rows blk..+7
+  const int bp = tp * kRP + bpl;
+  const int wq = tq * kRQ + wave * 32;  // MFMA: columns wq..+31, all 64 rows
+  const int Q = pr.Q, P = pr.P;
+  const bool qok = wq < Q;  // uniform
   const int mb0 = s * pr.kps;
   const int mb1 = (mb0 + pr.kps) < pr.MB ? (mb0 + pr.kps) : pr.MB;
+  // uniform byte strides per k-block and per-thread byte offsets (all below 2^31: one k-block
+  // of X is Q * 64 bytes, one dA row 8 P bytes)
+  const int sh = 5 - pr.logPg;  // >= 0: a k-block holds 2^sh sibling groups, < 0: a group 2^-sh k-blocks
+  const uint32_t xst = static_cast<uint32_t>(Q) * 64u, mst = static_cast<uint32_t>(P) * 4u, dst = static_cast<uint32_t>(P) * 8u;
+  const uint32_t xo = static_cast<uint32_t>((((qok ? wq : 0) + lr) * 32 + lk) * 2);
+  const uint32_t mo = static_cast<uint32_t>(bp * 4);
+  const uint32_t dso = static_cast<uint32_t>(((sh >= 0 ? (blk >> pr.logPg) : 0) * 2 * P + bp) * 4);
+  const uint32_t dno = dso + static_cast<uint32_t>(P * 4);
+  const uint32_t gmask = (pr.logPg < 31 ? (1u << pr.logPg) : 0u) - 1u;
+  const int dFb1 = pr.Fg + 1 - static_cast<int>(static_cast<uint32_t>(blk) & gmask);
+  RouteRaw r[kRKB];  // bits: the whole mask word (shifted where it is used, not where it is loaded)
+  uint4_t x[kRKB][2];
+  // the k-block's base is made opaque in scalar registers and the thread's offset in a vector
+  // register, so that the compiler neither folds one into the other nor widens the offset: the
+  // loads take the (scalar base, 32-bit vector offset) form and cost no address arithmetic
+  typedef const __attribute__((address_space(1))) char* gptr_t;
+  auto at = [](const void* base, uint32_t row, uint32_t stride, uint32_t off) __attribute__((always_inline)) {
+    uint64_t v = reinterpret_cast<uint64_t>(base) + static_cast<uint64_t>(row) * stride;
+    asm("" : "+s"(v));
+    asm("" : "+v"(off));
+    return (gptr_t)v + off;
+  };
+  auto load_raw = [&](RouteRaw& d, int mb) __attribute__((always_inline)) {
+    const uint32_t row = sh >= 0 ? (static_cast<uint32_t>(mb) << sh) : (static_cast<uint32_t>(mb) >> -sh);
+    d.bits = *(const __attribute__((address_space(1))) uint32_t*)at(pr.mask, mb, mst, mo);
+    d.ds = *(const __attribute__((address_space(1))) float*)at(pr.dA, row, dst, dso);
+    d.dn = *(const __attribute__((address_space(1))) float*)at(pr.dA, row, dst, dno);
+  };
+  auto load_x = [&](uint4_t (&d)[2], int mb) __attribute__((always_inline)) {
+    gptr_t p = at(pr.X, mb, xst, xo);
+#pragma unroll
+    for (int f = 0; f < 2; ++f) d[f] = *(const __attribute__((address_space(1))) uint4_t*)(p + f * (16 * 32 * 2));
+  };
+  // tr_route_spread's row sets without its selects: with e = min(max(dF + 1, 0), 9) the low e
+  // bits are the neighbour rows and the self row, the low e - 1 bits the neighbour rows
+  auto spread = [&](const RouteRaw& d, int mb) __attribute__((always_inline)) {
+    const int jm = static_cast<int>((static_cast<uint32_t>(mb) << 5) & gmask);  // uniform; 0 for groups <= 32 rows
+    const int e1 = dFb1 - jm, e = e1 < 0 ? 0 : (e1 > 9 ? 9 : e1);
+    const uint32_t both = (1u << e) - 1u, nm = both >> 1, b8 = (d.bits >> blk) & 0xffu;
+    return RouteSpread{lut[b8 & nm], lut[b8 & (both ^ nm)]};
+  };
   float4_t acc[4][2];
   tl_zero(acc);
-  struct Grp {
-    uint4_t x[kRG][2];
-    RouteRaw r[kRG][4];
-  };
-  auto load = [&](Grp& g, int mbs) {
-#pragma unroll
-    for (int u = 0; u < kRG; ++u) {
-      const int mb = (mbs + u) < mb1 ? (mbs + u) : (mb1 - 1);
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-        g.x[u][f] = *reinterpret_cast<const uint4_t*>(pr.X + ((static_cast<int64_t>(mb) * Q + wq + f * 16 + lr) * 32 + lk));
-#pragma unroll
-      for (int fm = 0; fm < 4; ++fm) g.r[u][fm] = tr_route_load(pr, mb, p0 + fm * 16 + lr, lk);
-    }
-  };
-  auto compute = [&](const Grp& g, int mbs) {
-#pragma unroll
-    for (int u = 0; u < kRG; ++u) {
-      if (mbs + u >= mb1) break;  // uniform
-#pragma unroll
-      for (int fm = 0; fm < 4; ++fm) {
-        const uint4_t a = tr_route_frag_lut(pr, g.r[u][fm], mbs + u, lk, lut);
-#pragma unroll
-        for (int fn = 0; fn < 2; ++fn) acc[fm][fn] = mfma16(a, g.x[u][fn], acc[fm][fn]);
-      }
-    }
-  };
   if (mb0 < mb1) {
-    Grp A, B;
-    load(A, mb0);
-    int it = 0;
-    for (int mbs = mb0; mbs < mb1; mbs += 2 * kRG) {
-      load(B, mbs + kRG);
-      compute(A, mbs);
-      if (mbs + kRG >= mb1) break;
-      load(A, mbs + 2 * kRG);
-      compute(B, mbs + kRG);
-      ++it;
-      if (it < 6 && (it & 1) == 0) RT_STAMP(it >> 1);
+    // prologue: every load of the first two stages goes out before the table is there (clamped:
+    // a short slab loads its last k-block again instead of branching).  The first stage's raw
+    // operands come first, into registers of their own; the rest in the order a stage issues
+    // them (per k-block the raw operands of the stage after next, then X of the next stage), so
+    // the first stage finds the load queue as every later stage does.
+    RouteRaw r0[kRKB];
+#pragma unroll
+    for (int u = 0; u < kRKB; ++u) load_raw(r0[u], (mb0 + u) < mb1 ? (mb0 + u) : (mb1 - 1));
+#pragma unroll
+    for (int u = 0; u < kRKB; ++u) {
+      load_raw(r[u], (mb0 + kRKB + u) < mb1 ? (mb0 + kRKB + u) : (mb1 - 1));
+      load_x(x[u], (mb0 + u) < mb1 ? (mb0 + u) : (mb1 - 1));
+      __builtin_amdgcn_sched_barrier(0);  // in this order
     }
+    tr_spread_lut_init(lut);
+    __syncthreads();
+    const int wr = rt_off(bpl, blk), rd = rt_off(lr, lk);  // rt_off(16 fm + lr, lk) = rd + 16 fm kRLd
+#pragma unroll
+    for (int u = 0; u < kRKB; ++u) {
+      const int mb = (mb0 + u) < mb1 ? (mb0 + u) : (mb1 - 1);
+      *reinterpret_cast<uint4_t*>(&gs[0][u][wr]) = tr_route_combine(pr, r0[u], spread(r0[u], mb));
+    }
+    __syncthreads();
+    // one stage: nc k-blocks to multiply, nb k-blocks of the next stage to build (and their X
+    // to load), nr k-blocks of the stage after that to load raw.  The table reads of k-block
+    // u + 1 go out with the A fragment reads of u + 1, before the MFMAs of u.
+    // nb and nr are all or nothing: past the slab's end the last k-block is loaded and built
+    // again (the prologue's clamp, one scalar min), so no register is written under a
+    // condition; what that builds is never multiplied.  Only the slab's last stage counts its
+    // MFMAs at run time, and it builds and loads nothing.
+    auto stage = [&](int buf, int mbs, auto nc, auto nb, auto nr) __attribute__((always_inline)) {
+      auto kb = [&](int mb) __attribute__((always_inline)) { return mb < mb1 ? mb : mb1 - 1; };
+      const bf16_t* gr = &gs[buf][0][rd];
+      bf16_t* gw = &gs[buf ^ 1][0][wr];
+      uint4_t a[2][4];
+      RouteSpread sp[2];
+#pragma unroll
+      for (int fm = 0; fm < 4; ++fm) a[0][fm] = *reinterpret_cast<const uint4_t*>(gr + fm * 16 * kRLd);
+      if (0 < nb) sp[0] = spread(r[0], kb(mbs + kRKB));
+#pragma unroll
+      for (int u = 0; u < kRKB; ++u) {
+        // the LDS reads of k-block u + 1 first, pinned there: left alone, the compiler sinks
+        // them down to the MFMAs that use them (one register set less) and every k-block
+        // waits for its own reads
+        if (u + 1 < kRKB) {
+#pragma unroll
+          for (int fm = 0; fm < 4; ++fm)
+            a[(u + 1) & 1][fm] = *reinterpret_cast<const uint4_t*>(gr + (u + 1) * kRP * kRLd + fm * 16 * kRLd);
+        }
+        if (u + 1 < kRKB && u + 1 < nb) sp[(u + 1) & 1] = spread(r[(u + 1) % kRKB], kb(mbs + kRKB + u + 1));
+        __builtin_amdgcn_sched_barrier(0);
+        if (u < nb) *reinterpret_cast<uint4_t*>(gw + u * kRP * kRLd) = tr_route_combine(pr, r[u], sp[u & 1]);
+        if (u < nr) load_raw(r[u], kb(mbs + 2 * kRKB + u));
+        if (u < nc) {  // uniform
+#pragma unroll
+          for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+            for (int fm = 0; fm < 4; ++fm) acc[fm][fn] = mfma16(a[u & 1][fm], x[u][fn], acc[fm][fn]);
+        }
+        if (u < nb) load_x(x[u], kb(mbs + kRKB + u));
+        // and nothing moves across a k-block: the raw loads would all sink to the stage's
+        // end, into fresh registers, and the next stage would wait for them
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    // every path below is uniform per block.  Each kind of stage has its own place in the
+    // control flow (a loop of stages with two more to come, then the last two written out),
+    // and all kinds issue their loads in the same order, so the load-queue depth the compiler
+    // counts on at a stage's top is a whole stage.
+    int buf = 0, it = 0, mbs = mb0;
+    auto next = [&](bool more) __attribute__((always_inline)) {
+      if (more) __syncthreads();
+      buf ^= 1;
+      mbs += kRKB;
+      ++it;
+      if (it < 6) RT_STAMP(it + 1);  // stamp 1: the prologue's end, stamp k + 1: the end of stage k
+    };
+    RT_STAMP(1);
+    const RtCount<kRKB> all;
+    const RtCount<0> none;
+    while (mb1 - mbs > 2 * kRKB) {
+      stage(buf, mbs, all, all, all);
+      next(true);
+    }
+    if (mb1 - mbs > kRKB) {
+      stage(buf, mbs, all, all, none);
+      next(true);
+    }
+    if (mb1 - mbs == kRKB) stage(buf, mbs, all, none, none);
+    else stage(buf, mbs, mb1 - mbs, none, none);
+    next(false);
   }
-  (void)P;
+  RT_STAMP(7);
+  if (!qok) return;
   float* out = pr.part + static_cast<int64_t>(s) * pr.P * Q;
+  const int p0 = tp * kRP;
 #pragma unroll
   for (int fm = 0; fm < 4; ++fm)
 #pragma unroll
@@ -1729,7 +1858,6 @@ __device__ __forceinline__ void tr_dw_route_reg_body(const TrDwProb& pr, int b, 
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj)
         out[(p0 + fm * 16 + (lane >> 4) * 4 + jj) * Q + wq + fn * 16 + lr] = acc[fm][fn][jj];
-  RT_STAMP(7);
 }
 #undef RT_STAMP
 
@@ -1904,16 +2032,21 @@ __global__ __launch_bounds__(256, 2) void tr_dw_all_kernel(TrDwLaunch a) {
   __shared__ __attribute__((aligned(16))) RouteLds gs;
   __shared__ uint4_t lut[256];
   const int b = blockIdx.x;
-  if (a.nroute > 0 && b < a.rwg[a.nroute]) {  // routed blocks: the fragment-spread table first
+  const bool pipe = a.route_impl == 2;  // that body fills the table itself, behind its first loads
+  if (!pipe && a.nroute > 0 && b < a.rwg[a.nroute]) {  // routed blocks: the fragment-spread table first
     tr_spread_lut_init(lut);
     __syncthreads();
   }
-  if (a.nroute > 0 && b < a.rwg[1]) {
-    if (a.route_impl == 1) tr_dw_route_reg_body(a.route[0], b, lut, a.prof);
-    else tr_dw_route_body(a.route[0], b, gs, lut, a.prof);
+  if (pipe && a.nroute > 0 && b < a.rwg[a.nroute]) {
+    // one copy of the body for both routed problems: the problem is picked into registers
+    const bool second = b >= a.rwg[1];  // uniform
+    TrDwProb pr = a.route[0];
+    if (second) pr = a.route[1];
+    tr_dw_route_pipe_body(pr, second ? b - a.rwg[1] : b, gs, lut, second ? nullptr : a.prof);
+  } else if (a.nroute > 0 && b < a.rwg[1]) {
+    tr_dw_route_body(a.route[0], b, gs, lut, a.prof);
   } else if (a.nroute > 1 && b < a.rwg[2]) {
-    if (a.route_impl == 1) tr_dw_route_reg_body(a.route[1], b - a.rwg[1], lut, nullptr);
-    else tr_dw_route_body(a.route[1], b - a.rwg[1], gs, lut, nullptr);
+    tr_dw_route_body(a.route[1], b - a.rwg[1], gs, lut, nullptr);
   } else {
     const int r = a.rwg[a.nroute];
     const int id = xcd_remap(b - r, static_cast<int>(gridDim.x) - r);

@@ -268,7 +268,8 @@ struct TrDwLaunch {
   TrDwProb route[2];
   int32_t nroute;
   int32_t rwg[3];       // block prefix of the routed problems
-  int32_t route_impl;   // 0: G^T tile built once per block in LDS; 1: built per wave in registers
+  int32_t route_impl;   // 2: build / load / multiply woven into one pipelined stage (the default),
+                        // 0: one after the other (the equality baseline)
   long long* prof;      // optional [route blocks][8] wall-clock stamps (diagnostics)
 };
 

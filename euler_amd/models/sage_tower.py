@@ -110,6 +110,8 @@ class _Tower:
                  "A0_kt": torch.empty(self.M * 2 * self.D, dtype=torch.bfloat16, device=device),
                  "mask0": torch.zeros((self.M // 32) * self.H0, **i32), "A1": self.A1, "dA1": self.dA1,
                  "gW0": self.gW0}
+            if os.environ.get("EULER_AMD_DW_ROUTE_IMPL"):  # body of the routed W0 problem (0: the baseline)
+                d["dw_route_impl"] = int(os.environ["EULER_AMD_DW_ROUTE_IMPL"])
             self._keep = d
             self.plan = hip().TowerPlan(d)
 
@@ -213,6 +215,8 @@ class UnsupSageTrainer:
             d[f"bfc_{x}"] = self.params[f"{t}.bfc"]
         if os.environ.get("EULER_AMD_DW_FOLD"):  # 0: the W1 / Wfc split-K slabs go through memory
             d["dw_fold"] = int(os.environ["EULER_AMD_DW_FOLD"])
+        if os.environ.get("EULER_AMD_DW_ROUTE_IMPL"):
+            d["dw_route_impl"] = int(os.environ["EULER_AMD_DW_ROUTE_IMPL"])
         self._pair_keep = d
         self.pair = hip().PairPlan(self.towers["gnn"].plan, self.towers["context_gnn"].plan, d)
         self.pair.opt(3)  # bf16 shadows of every weight
