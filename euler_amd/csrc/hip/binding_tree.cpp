@@ -89,6 +89,93 @@ int plan_route_impl(const PlanDict& pd) {
   return static_cast<int>(impl);
 }
 
+// the optimizer inside the dW launch, the key every plan shares: dw_opt_fuse (1: the single-process
+// step runs the split-K reduce and the update in the dW launch, where the plan allows it; 0: the
+// optimizer launch of its own)
+bool plan_fuse_key(const PlanDict& pd) {
+  const int64_t f = pd.has("dw_opt_fuse") ? pd.geti("dw_opt_fuse") : 1;
+  TORCH_CHECK(f == 0 || f == 1, pd.name(), ": dw_opt_fuse must be 0 or 1");
+  return f == 1;
+}
+
+// TrDwOpt of dW launch L from the optimizer arguments o of tr_opt mode 2: each flat segment is
+// found by the `part` slabs it sums.  Stored-G problems must be folded (their blocks update the
+// tile themselves); vector segments, then the routed problems' segments in the launch's order,
+// go to trailing blocks.  False: this launch cannot carry the optimizer (an unfolded stored-G
+// problem, or a problem or segment without its counterpart).  sync_lines: hand-off lines needed.
+bool fill_dw_opt(const TrDwLaunch& L, const TrOptArgs& o, TrDwOpt& f, int64_t& sync_lines) {
+  f = TrDwOpt{};
+  const TrSeg* rseg[2] = {nullptr, nullptr};
+  bool pseg[kTrMaxProbs] = {};
+  int nvec = 0;
+  for (int k = 0; k < o.nseg; ++k) {
+    const TrSeg& g = o.seg[k];
+    if (g.cols == 0) {
+      f.seg[nvec++] = g;
+      continue;
+    }
+    bool found = false;
+    for (int r = 0; r < L.nroute && !found; ++r)
+      if (L.route[r].part == g.part && !rseg[r]) {
+        rseg[r] = &g;
+        found = true;
+      }
+    for (int i = 0; i < L.plain.n && !found; ++i) {
+      const TrDwProb& p = L.plain.p[i];
+      if (p.part != g.part || pseg[i]) continue;
+      if (p.F < 1 || g.S != 1 || g.rows != p.P || g.cols != p.Q || g.off % 4 != 0) return false;
+      f.fseg[i] = TrFoldSeg{g.off, g.sh, g.shT};
+      pseg[i] = true;
+      found = true;
+    }
+    if (!found) return false;
+  }
+  for (int i = 0; i < L.plain.n; ++i)
+    if (!pseg[i]) return false;
+  f.rseg0 = nvec;
+  f.nseg = nvec + L.nroute;
+  if (f.nseg < 1 || f.nseg > kTrMaxSegs) return false;
+  sync_lines = 2;
+  for (int r = 0; r < L.nroute; ++r) {
+    if (!rseg[r]) return false;
+    f.seg[nvec + r] = *rseg[r];
+    const TrDwProb& p = L.route[r];
+    sync_lines += static_cast<int64_t>(p.P / 64) * ((p.Q + 127) / 128);
+  }
+  int blk = 0;
+  for (int k = 0; k < f.nseg; ++k) {
+    f.seg[k].blk0 = blk;
+    blk += tr_seg_prepare(f.seg[k]);
+  }
+  f.nblk = blk;
+  f.p = o.p;
+  f.m = o.m;
+  f.v = o.v;
+  f.step = o.step;
+  f.lr = o.lr;
+  f.b1 = o.b1;
+  f.b2 = o.b2;
+  f.eps = o.eps;
+  f.wd = o.wd;
+  f.grad_scale = o.grad_scale;
+  f.kind = o.kind;
+  f.head_part = o.head_part;
+  f.nhead = o.nhead;
+  f.loss_acc = o.loss_acc;
+  f.counts = o.counts;
+  f.loss_out = o.loss_out;
+  f.stat_f = o.stat_f;
+  f.nsync = static_cast<int32_t>(sync_lines);
+  f.timeout = kTrFuseWaitTicks;
+  return o.nhead > 0;
+}
+
+// the status word of a plan's hand-off state (0: every wait of every fused launch so far was
+// met); synchronises
+int64_t fuse_status(const torch::Tensor& sync) {
+  return sync.defined() ? sync[kTrSyncLine].item<int64_t>() : 0;
+}
+
 class TreePlan : private PlanDict {
  public:
   explicit TreePlan(py::dict d) : PlanDict(d, "TreePlan") {
@@ -124,7 +211,19 @@ class TreePlan : private PlanDict {
     build_head();
     build_dw();
     build_opt();
+    // the optimizer in the dW launch of all problems (fill_dw_opt), unless the step is pipelined
+    // (its optimizer launch carries the next batch's gather)
+    TrDwLaunch L = launch_of(all_problems());
+    TrDwOpt f;
+    int64_t lines = 0;
+    if (plan_fuse_key(*this) && !pipeline_ok() && fill_dw_opt(L, opt_, f, lines)) {
+      fused_ = true;
+      sync_ = zeros(lines * kTrSyncLine, torch::kInt32);
+    }
   }
+
+  bool fused() const { return fused_; }
+  int64_t fuse_error() const { return fuse_status(sync_); }
 
   void sample() {
     const c10::DeviceGuard g(device());
@@ -166,15 +265,58 @@ class TreePlan : private PlanDict {
     tree_ok(eh_tr_bwd(&bwd1_, cur_stream()), "tr_bwd");
   }
 
-  // dW of the given problems, one launch: routed problems first, the others grouped
-  void dw(std::vector<int64_t> which, c10::optional<torch::Tensor> prof) {
+  // dW of the given problems, one launch: routed problems first, the others grouped.
+  // fuse (a fused() plan, every problem): the launch also runs the optimizer, what opt(2,
+  // grad_scale) would do after it
+  void dw(std::vector<int64_t> which, c10::optional<torch::Tensor> prof, bool fuse, double grad_scale) {
     const c10::DeviceGuard g(device());
-    TrDwLaunch L{};
-    L.route_impl = route_impl_;
+    TrDwLaunch L = launch_of(which);
     if (prof.has_value()) {
       need(*prof, torch::kInt64, -1, "prof");
       L.prof = reinterpret_cast<long long*>(prof->data_ptr<int64_t>());
     }
+    if (fuse) {
+      TORCH_CHECK(fused_ && L.nroute + L.plain.n == (int)probs_.size(),
+                  "dw: the optimizer runs in the dW launch of every problem of a fused() plan only");
+      TrOptArgs o = opt_;
+      o.grad_scale = static_cast<float>(grad_scale);
+      int64_t lines = 0;
+      TORCH_CHECK(fill_dw_opt(L, o, L.opt, lines) && lines * kTrSyncLine == sync_.numel(), "dw: fused plan changed");
+      L.opt.sync = reinterpret_cast<uint32_t*>(sync_.data_ptr<int32_t>());
+      L.fuse = 1;
+    }
+    if (L.nroute == 0 && L.plain.n == 0) return;
+    tree_ok(eh_tr_dw(&L, cur_stream()), fuse ? "tr_dw+opt" : "tr_dw");
+  }
+
+  // workgroups of the dW launch of every problem (fuse: with its trailing optimizer blocks)
+  int64_t dw_blocks(bool fuse) const {
+    TORCH_CHECK(!fuse || fused_, "dw_blocks: the plan is not fused()");
+    int64_t n = 0;
+    for (size_t i = 0; i < probs_.size(); ++i) {
+      const TrDwProb& p = probs_[i];
+      if (p.route) n += route_blocks(static_cast<int64_t>(i));
+      else if (p.F > 0) n += static_cast<int64_t>(p.P / 32) * (p.Q / 32);
+      else n += static_cast<int64_t>((p.P + 63) / 64) * ((p.Q + 63) / 64) * p.S;
+    }
+    if (fuse) {
+      TrDwOpt f;
+      int64_t lines = 0;
+      TORCH_CHECK(fill_dw_opt(launch_of(all_problems()), opt_, f, lines), "dw_blocks: fused plan changed");
+      n += f.nblk;
+    }
+    return n;
+  }
+
+  std::vector<int64_t> all_problems() const {
+    std::vector<int64_t> w(probs_.size());
+    for (size_t i = 0; i < w.size(); ++i) w[i] = static_cast<int64_t>(i);
+    return w;
+  }
+
+  TrDwLaunch launch_of(const std::vector<int64_t>& which) const {
+    TrDwLaunch L{};
+    L.route_impl = route_impl_;
     for (int64_t i : which) {
       TORCH_CHECK(i >= 0 && i < (int64_t)probs_.size(), "dw: problem index out of range");
       if (probs_[i].route) {
@@ -185,8 +327,7 @@ class TreePlan : private PlanDict {
         L.plain.p[L.plain.n++] = probs_[i];
       }
     }
-    if (L.nroute == 0 && L.plain.n == 0) return;
-    tree_ok(eh_tr_dw(&L, cur_stream()), "tr_dw");
+    return L;
   }
 
   std::vector<int64_t> problems(bool route) const {
@@ -308,6 +449,8 @@ class TreePlan : private PlanDict {
   torch::Tensor roots_cur_;  // the forward's copy of the batch's roots (read by the head)
   TrOptArgs opt_{};
   torch::Tensor g16_, grad_;
+  bool fused_ = false;  // plan key dw_opt_fuse, where the launch of all problems can carry the optimizer
+  torch::Tensor sync_;  // hand-off state of the fused launch (TrDwOpt::sync)
 
   int64_t Hin(int k) const { return k == 0 ? D_ : dims_[k - 1]; }
 
@@ -725,7 +868,12 @@ class TowerPlan : private PlanDict {
     o.counts = nullptr;
     o.nsample = 0;
     o.kind = 2;
+    plan_fuse_key(*this);  // accepted and checked; bwd() is a reduce into gW0 (mode 0), which keeps tr_opt
   }
+
+  // the tower's backward hands a gradient to torch's optimizer: no optimizer in its dW launch
+  bool fused() const { return false; }
+  int64_t fuse_error() const { return 0; }
 
   // refresh the bf16 fm shadow of W0 from the fp32 master (call after each update)
   void shadow() {
@@ -894,7 +1042,16 @@ class PairPlan : private PlanDict {
     o.stat_f = ptr<float>("mrr_sum", torch::kFloat32, 1);
     o.counts = nullptr;
     o.nsample = 0;
+    TrDwOpt f;
+    int64_t lines = 0;
+    if (plan_fuse_key(*this) && fill_dw_opt(L_, opt_, f, lines)) {
+      fused_ = true;
+      sync_ = zeros(lines * kTrSyncLine, torch::kInt32);
+    }
   }
+
+  bool fused() const { return fused_; }
+  int64_t fuse_error() const { return fuse_status(sync_); }
 
   void sample() {
     const c10::DeviceGuard g(device());
@@ -910,10 +1067,20 @@ class PairPlan : private PlanDict {
     const c10::DeviceGuard g(device());
     tree_ok(eh_tr_pair_head(&head_, cur_stream()), "pair head");
   }
-  void dw() {
+  // fuse (a fused() plan): the launch also runs the optimizer, what opt(2, grad_scale) would do
+  void dw(bool fuse, double grad_scale) {
     const c10::DeviceGuard g(device());
     TrDwLaunch L = L_;
-    tree_ok(eh_tr_dw(&L, cur_stream()), "pair dw");
+    if (fuse) {
+      TORCH_CHECK(fused_, "pair dw: the plan is not fused()");
+      TrOptArgs o = opt_;
+      o.grad_scale = static_cast<float>(grad_scale);
+      int64_t lines = 0;
+      TORCH_CHECK(fill_dw_opt(L, o, L.opt, lines) && lines * kTrSyncLine == sync_.numel(), "pair dw: fused plan changed");
+      L.opt.sync = reinterpret_cast<uint32_t*>(sync_.data_ptr<int32_t>());
+      L.fuse = 1;
+    }
+    tree_ok(eh_tr_dw(&L, cur_stream()), fuse ? "pair dw+opt" : "pair dw");
   }
   // 0: split-K reduce into the flat gradient; 1: optimizer from it (scaled); 2: both; 3: shadows
   void opt(int mode, double grad_scale) {
@@ -952,7 +1119,8 @@ class PairPlan : private PlanDict {
   TrDwLaunch L_{};
   int plain_[4] = {0, 0, 0, 0};
   TrOptArgs opt_{};
-  torch::Tensor step_, grad_keep_;
+  torch::Tensor step_, grad_keep_, sync_;
+  bool fused_ = false;
 
   void tower(TrPairTower& t, const TowerPlan& tp, const std::string& x) {
     const int64_t R = tp.R();
@@ -1016,7 +1184,11 @@ void register_tree_ops(py::module& m) {
       .def("fwd_blocks", [](const TreePlan& t) { return t.fwd_blocks(); })
       .def("head", &TreePlan::head, py::arg("prof") = py::none(), py::arg("with_sample") = false)
       .def("bwd", &TreePlan::bwd)
-      .def("dw", &TreePlan::dw, py::arg("which"), py::arg("prof") = py::none())
+      .def("dw", &TreePlan::dw, py::arg("which"), py::arg("prof") = py::none(), py::arg("fuse") = false,
+           py::arg("grad_scale") = 1.0)
+      .def("fused", &TreePlan::fused)
+      .def("dw_blocks", &TreePlan::dw_blocks, py::arg("fuse"))
+      .def("fuse_error", &TreePlan::fuse_error)
       .def("route_blocks", &TreePlan::route_blocks)
       .def("opt", &TreePlan::opt, py::arg("mode"), py::arg("grad_scale") = 1.0, py::arg("with_sample") = false,
            py::arg("with_gather") = false)
@@ -1035,13 +1207,17 @@ void register_tree_ops(py::module& m) {
       .def("shadow", &TowerPlan::shadow)
       .def("sample", &TowerPlan::sample)
       .def("fwd", &TowerPlan::fwd)
-      .def("bwd", &TowerPlan::bwd);
+      .def("bwd", &TowerPlan::bwd)
+      .def("fused", &TowerPlan::fused)
+      .def("fuse_error", &TowerPlan::fuse_error);
   py::class_<PairPlan>(m, "PairPlan")
       .def(py::init<const TowerPlan&, const TowerPlan&, py::dict>(), py::keep_alive<1, 2>(), py::keep_alive<1, 3>())
       .def("sample", &PairPlan::sample)
       .def("fwd", &PairPlan::fwd)
       .def("head", &PairPlan::head)
-      .def("dw", &PairPlan::dw)
+      .def("dw", &PairPlan::dw, py::arg("fuse") = false, py::arg("grad_scale") = 1.0)
+      .def("fused", &PairPlan::fused)
+      .def("fuse_error", &PairPlan::fuse_error)
       .def("opt", &PairPlan::opt, py::arg("mode"), py::arg("grad_scale") = 1.0)
       .def("set_lr", &PairPlan::set_lr)
       .def("set_grad", &PairPlan::set_grad)

@@ -1578,10 +1578,45 @@ struct RouteStage {
 
 typedef bf16_t RouteLds[2][kRKB][kRP * kRLd];
 
+// The slab tile of one wave of a routed block, and the hand-off to the trailing optimizer blocks
+// of a fused launch (ready != nullptr: the tile's counter).  Fused: the slab goes out as
+// agent-scope relaxed atomic stores (write-through, nothing left dirty in this XCD's L2; staging
+// the tile in LDS for 16-B stores measured 0.15 us slower, profiles/dw_opt_fuse/README.md), every
+// wave waits for its own stores, and behind the workgroup barrier one lane adds 1 to the counter
+// of the 64 x 128 tile: the add comes after the wait of every wave it signals for.  Waves past Q
+// (qok false) store nothing and join the barrier.
+__device__ __forceinline__ void tr_route_store(const float4_t (&acc)[4][2], float* out, int Q, bool qok,
+                                               uint32_t* ready) {
+  const int lane = threadIdx.x & 63, lr = lane & 15;
+  if (!ready) {
+    if (!qok) return;
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) out[(fm * 16 + (lane >> 4) * 4 + jj) * Q + fn * 16 + lr] = acc[fm][fn][jj];
+    return;
+  }
+  if (qok) {
+#pragma unroll
+    for (int fm = 0; fm < 4; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < 2; ++fn)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+          __hip_atomic_store(&out[(fm * 16 + (lane >> 4) * 4 + jj) * Q + fn * 16 + lr], acc[fm][fn][jj],
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(ready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 #define RT_STAMP(k) \
   if (prof && threadIdx.x == 0) prof[static_cast<int64_t>(b) * 8 + (k)] = static_cast<long long>(wall_clock64())
 __device__ __forceinline__ void tr_dw_route_body(const TrDwProb& pr, int b, RouteLds& gs, const uint4_t* lut,
-                                                 long long* prof) {
+                                                 long long* prof, uint32_t* ready) {
   RT_STAMP(0);
   // XCD-aware: the tiles of one split (which read the same X rows) share b % 8
   const int j = b >> 3;
@@ -1653,16 +1688,9 @@ __device__ __forceinline__ void tr_dw_route_body(const TrDwProb& pr, int b, Rout
     }
   }
   RT_STAMP(7);
-  if (!qok) return;
   float* out = pr.part + static_cast<int64_t>(s) * pr.P * Q;
-  const int p0 = tp * kRP;
-#pragma unroll
-  for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj)
-        out[(p0 + fm * 16 + (lane >> 4) * 4 + jj) * Q + wq + fn * 16 + lr] = acc[fm][fn][jj];
+  tr_route_store(acc, out + static_cast<int64_t>(tp * kRP) * Q + wq, static_cast<int>(Q), qok,
+                 ready ? ready + tile * kTrSyncLine : nullptr);
 }
 
 // ----------------------------------------------------------------------------
@@ -1696,7 +1724,7 @@ struct RtCount {
 };
 
 __device__ __forceinline__ void tr_dw_route_pipe_body(const TrDwProb& pr, int b, RouteLds& gs, uint4_t* lut,
-                                                      long long* prof) {
+                                                      long long* prof, uint32_t* ready) {
   RT_STAMP(0);
   const int j = b >> 3;
   const int tile = j % pr.ntiles;
@@ -1848,16 +1876,9 @@ __device__ __forceinline__ void tr_dw_route_pipe_body(const TrDwProb& pr, int b,
     next(false);
   }
   RT_STAMP(7);
-  if (!qok) return;
   float* out = pr.part + static_cast<int64_t>(s) * pr.P * Q;
-  const int p0 = tp * kRP;
-#pragma unroll
-  for (int fm = 0; fm < 4; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < 2; ++fn)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj)
-        out[(p0 + fm * 16 + (lane >> 4) * 4 + jj) * Q + wq + fn * 16 + lr] = acc[fm][fn][jj];
+  tr_route_store(acc, out + static_cast<int64_t>(tp * kRP) * Q + wq, static_cast<int>(Q), qok,
+                 ready ? ready + tile * kTrSyncLine : nullptr);
 }
 #undef RT_STAMP
 
@@ -1942,10 +1963,63 @@ __device__ __forceinline__ void tr_dw_plain_body(const TrDwProb& pr, int local) 
 // per thread, 8 threads per row; a 16-lane group of ds_read_b128 covers 4 rows x 16 columns
 // that lie on 64 distinct banks with or without the swap (bit 2 is equal within 4 rows).
 // ----------------------------------------------------------------------------
+// One parameter's optimizer update from its summed gradient g, shared by the optimizer launch
+// (tr_opt_tile) and the blocks of a fused dW launch; A: TrOptArgs or TrDwOpt.
+template <class A>
+__device__ __forceinline__ void tr_opt_update(const A& a, float g, float& p, float& m, float& v) {
+  // Which multiply-add pairs are fused is written out (fmaf) and nothing else may be contracted:
+  // left to the compiler the choice follows the surrounding code, and the two callers would
+  // round differently.  These are the roundings the optimizer launch has always made.
+#pragma clang fp contract(off)
+  const float t = static_cast<float>(a.step[0]);
+  const float gi = fmaf(a.wd, p, g * a.grad_scale);
+  float d;
+  if (a.kind == 0) {
+    const float bc1 = 1.f - __powf(a.b1, t), bc2 = 1.f - __powf(a.b2, t);
+    m = fmaf(a.b1, m, (1.f - a.b1) * gi);
+    v = fmaf(a.b2, v, (1.f - a.b2) * gi * gi);
+    d = a.lr * (m / bc1) / (sqrtf(v / bc2) + a.eps);
+  } else if (a.kind == 1) {
+    v = fmaf(gi, gi, v);
+    d = a.lr * gi / (sqrtf(v) + a.eps);
+  } else if (a.kind == 2) {
+    d = a.lr * gi;
+  } else {
+    m = fmaf(a.b1, m, gi);
+    d = a.lr * m;
+  }
+  p -= d;
+}
+
+// bf16 shadows of the 8 x 32 weight tile at (r0, c0), staged in tile_s (written and barriered by
+// the caller), by the 64 threads t = 0..63: rows as 16-B fm chunks (t < 32), columns of the
+// transpose (t >= 32, where shT is set)
+__device__ __forceinline__ void tr_opt_shadow(uint16_t* sh, uint16_t* shT, int rows, int cols, int r0, int c0,
+                                              const float (*tile_s)[33], int t) {
+  if (t < 32) {
+    const int row = t >> 2, kc = (t & 3) * 8;
+    float t8[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t8[k] = tile_s[row][kc + k];
+    *reinterpret_cast<uint4_t*>(sh + fm_off(r0 + row, c0 + kc, cols)) = pack_bf16x8(t8);
+  } else if (t < 64 && shT) {
+    const int col = t - 32;
+    float t8[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t8[k] = tile_s[k][col];
+    *reinterpret_cast<uint4_t*>(shT + fm_off(c0 + col, r0, rows)) = pack_bf16x8(t8);
+  }
+}
+
 static_assert(sizeof(RouteLds) >= kTrFoldLds, "the fold's slots alias the routed body's G tile");
+static_assert(kTrFoldLds >= 32 * 33 * 4, "the fused fold stages its 32 x 32 tile in the slots");
 __device__ __forceinline__ int tr_fold_off(int row, int col) { return row * 32 + (col ^ ((row & 4) << 2)); }
 
-__device__ __forceinline__ void tr_dw_fold_body(const TrDwProb& pr, int tile, float* slots) {
+// fuse (a fused launch; fz: the problem's flat segment): the block applies the optimizer to its tile instead of storing
+// the `part` slab: the sum below is the S == 1 gradient tr_opt_tile<2> would read back, and the
+// update and the shadow writes are the code it runs (tr_opt_update, tr_opt_shadow).
+__device__ __forceinline__ void tr_dw_fold_body(const TrDwProb& pr, int tile, float* slots, const TrDwOpt& o,
+                                                const TrFoldSeg& fz, bool fuse) {
   const int tp = tile / pr.tiles_q, tq = tile - tp * pr.tiles_q;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int lr = lane & 15, lk = (lane >> 4) * 8;
@@ -2023,41 +2097,40 @@ __device__ __forceinline__ void tr_dw_fold_body(const TrDwProb& pr, int tile, fl
   // tile per 8 lanes
   const int row = tid >> 3, c4 = (tid & 7) * 4;
   const float* src = slots + tr_fold_off(row, c4);
+  float4_t pw = {0.f, 0.f, 0.f, 0.f}, mw = pw, vw = pw;
+  const int64_t fi = fuse ? fz.off + (p0 + row) * Q + q0 + c4 : 0;
+  if (fuse) {  // uniform; the optimizer slots' latency overlaps the slot sum
+    pw = *reinterpret_cast<const float4_t*>(o.p + fi);
+    mw = *reinterpret_cast<const float4_t*>(o.m + fi);
+    vw = *reinterpret_cast<const float4_t*>(o.v + fi);
+  }
   float4_t g = {0.f, 0.f, 0.f, 0.f};
   for (int sl = 0; sl < F; ++sl) g += *reinterpret_cast<const float4_t*>(src + sl * (32 * 32));
-  *reinterpret_cast<float4_t*>(pr.part + (p0 + row) * Q + q0 + c4) = g;
-}
-
-__global__ __launch_bounds__(256, 2) void tr_dw_all_kernel(TrDwLaunch a) {
-  __shared__ __attribute__((aligned(16))) RouteLds gs;
-  __shared__ uint4_t lut[256];
-  const int b = blockIdx.x;
-  const bool pipe = a.route_impl == 2;  // that body fills the table itself, behind its first loads
-  if (!pipe && a.nroute > 0 && b < a.rwg[a.nroute]) {  // routed blocks: the fragment-spread table first
-    tr_spread_lut_init(lut);
-    __syncthreads();
+  if (!fuse) {
+    *reinterpret_cast<float4_t*>(pr.part + (p0 + row) * Q + q0 + c4) = g;
+    return;
   }
-  if (pipe && a.nroute > 0 && b < a.rwg[a.nroute]) {
-    // one copy of the body for both routed problems: the problem is picked into registers
-    const bool second = b >= a.rwg[1];  // uniform
-    TrDwProb pr = a.route[0];
-    if (second) pr = a.route[1];
-    tr_dw_route_pipe_body(pr, second ? b - a.rwg[1] : b, gs, lut, second ? nullptr : a.prof);
-  } else if (a.nroute > 0 && b < a.rwg[1]) {
-    tr_dw_route_body(a.route[0], b, gs, lut, a.prof);
-  } else if (a.nroute > 1 && b < a.rwg[2]) {
-    tr_dw_route_body(a.route[1], b - a.rwg[1], gs, lut, nullptr);
-  } else {
-    const int r = a.rwg[a.nroute];
-    const int id = xcd_remap(b - r, static_cast<int>(gridDim.x) - r);
-    // constant indices only (no dynamic indexing of kernel arguments)
-    TrDwProb pr = a.plain.p[0];
 #pragma unroll
-    for (int i = 1; i < kTrMaxProbs; ++i)
-      if (a.plain.n > i && id >= a.plain.p[i].wg0) pr = a.plain.p[i];
-    if (pr.F > 0) tr_dw_fold_body(pr, id - pr.wg0, reinterpret_cast<float*>(&gs[0][0][0]));  // uniform per block
-    else tr_dw_plain_body(pr, id - pr.wg0);
+  for (int j = 0; j < 4; ++j) {
+    float gs = 0.f;  // the one-slab sum of tr_opt_tile
+    gs += g[j];
+    float pj = pw[j], mj = mw[j], vj = vw[j];
+    tr_opt_update(o, gs, pj, mj, vj);
+    pw[j] = pj;
+    mw[j] = mj;
+    vw[j] = vj;
   }
+  *reinterpret_cast<float4_t*>(o.p + fi) = pw;
+  *reinterpret_cast<float4_t*>(o.m + fi) = mw;
+  *reinterpret_cast<float4_t*>(o.v + fi) = vw;
+  if (!fz.sh) return;  // uniform
+  // four 8 x 32 sub-tiles, one per wave, staged in the LDS the slots no longer need
+  __syncthreads();
+  float(*st)[33] = reinterpret_cast<float(*)[33]>(slots);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) st[row][c4 + j] = pw[j];
+  __syncthreads();
+  tr_opt_shadow(fz.sh, fz.shT, pr.P, pr.Q, p0 + wave * 8, q0, st + wave * 8, lane);
 }
 
 // ----------------------------------------------------------------------------
@@ -2068,13 +2141,45 @@ __global__ __launch_bounds__(256, 2) void tr_dw_all_kernel(TrDwLaunch a) {
 // a separate instantiation so the plain optimizer keeps its small register footprint
 // one 8 x 32 (or 256-element) tile of the optimizer launch: split-K reduce and / or the
 // update, the bf16 shadows of weight tiles; block 0 also reduces the head statistics
-template <int MODE>
-__device__ __forceinline__ void tr_opt_tile(const TrOptArgs& a, int b, float (*tile_s)[33]) {
+// The wait of a routed-segment tile block of a fused dW launch for the `want` producers of its
+// routed tile.  Consumer form: one lane's relaxed agent-scope poll (s_sleep between polls, the
+// other waves sit at the barrier), ONE agent acquire, the wait for its invalidate, the workgroup
+// barrier; the slab loads that follow are agent-scope loads too.  Bounded: past a.timeout ticks
+// of the wall clock the block flags the plan's status word, poisons the step's loss and goes on
+// with whatever the slabs hold: a wrong, flagged result, never a hang (as in xgmi_ar.hip).
+__device__ __forceinline__ void tr_fuse_wait(const TrDwOpt& a, const uint32_t* cnt, uint32_t want) {
+  if (threadIdx.x == 0) {
+    const long long t0 = wall_clock64();
+    while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want) {
+      if (wall_clock64() - t0 > a.timeout) {
+        __hip_atomic_store(a.sync + kTrSyncLine, kTrFuseTimeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.loss_out, __builtin_nanf(""), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(8);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+}
+
+// FUSE (A = TrDwOpt, MODE 2): a trailing block of the dW launch; the slabs are read with
+// agent-scope loads, and a tile of a routed segment first waits for its producers.
+template <bool FUSE>
+__device__ __forceinline__ float tr_slab_load(const float* p) {
+  if constexpr (FUSE) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return *p;
+}
+
+template <int MODE, bool FUSE = false, class A = TrOptArgs>
+__device__ __forceinline__ void tr_opt_tile(const A& a, int b, float (*tile_s)[33]) {
+  static_assert(!FUSE || MODE == 2, "trailing blocks run the fused reduce + update");
   const int tid = threadIdx.x;
   if (b == 0 && tid < 64 && MODE != 3 && a.nhead > 0) {
     // head statistics: reduce (modes 0/2) the per-block partials; hand the loss over (1/2);
     // nhead == 0: a segment-subset reduce launch that leaves them to another launch
-    if (MODE != 1) {
+    if constexpr (MODE != 1) {
       float v[4] = {0.f, 0.f, 0.f, 0.f};
       for (int k = tid; k < a.nhead; k += 64)
 #pragma unroll
@@ -2097,9 +2202,14 @@ __device__ __forceinline__ void tr_opt_tile(const TrOptArgs& a, int b, float (*t
     }
   }
   TrSeg sg = a.seg[0];
+  int ks = 0;
 #pragma unroll
   for (int k = 1; k < kTrMaxSegs; ++k)
-    if (k < a.nseg && b >= a.seg[k].blk0) sg = a.seg[k];
+    if (k < a.nseg && b >= a.seg[k].blk0) {
+      sg = a.seg[k];
+      ks = k;
+    }
+  (void)ks;
   const int local = b - sg.blk0;
   int64_t i;
   int r = 0, c = 0;
@@ -2127,22 +2237,29 @@ __device__ __forceinline__ void tr_opt_tile(const TrOptArgs& a, int b, float (*t
     m = a.m[i];
     v = a.v[i];
   }
+  if constexpr (FUSE) {
+    if (ks >= a.rseg0) {  // uniform: a routed segment; the 64 x 128 routed tile this 8 x 32 tile lies in
+      const int rt = (r >> 6) * ((sg.cols + 127) >> 7) + (c >> 7);  // the same for the block's 8 rows x 32 columns
+      const int c0 = ks == a.rseg0 ? a.cnt0[0] : a.cnt0[1];         // constant indices only
+      tr_fuse_wait(a, a.sync + static_cast<int64_t>(c0 + rt) * kTrSyncLine, static_cast<uint32_t>(sg.S));
+    }
+  }
   if (MODE != 3) {
     float g;
-    if (MODE != 1) {
+    if constexpr (MODE != 1) {
       // split-K slabs: 16 loads in flight, indices clamped (no branch around a load; 32 in
       // flight measured slower: 9.38 vs 8.75 us, profiles/r3_headline/)
       const float* src = sg.part + (i - sg.off);
       g = 0.f;
       // one slab (a dW problem summed in its blocks, tr_dw_fold_body): one load; uniform
-      if (sg.S == 1) g += src[0];
+      if (sg.S == 1) g += tr_slab_load<FUSE>(src);
       // slabs sub, sub + grp, ... (grp == 1: all of them, in order)
       for (int s0 = sub; sg.S > 1 && s0 < sg.S; s0 += 16 * grp) {
         float v[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
           const int sl = s0 + u * grp;
-          v[u] = src[static_cast<int64_t>(sl < sg.S ? sl : sg.S - 1) * sg.n];
+          v[u] = tr_slab_load<FUSE>(src + static_cast<int64_t>(sl < sg.S ? sl : sg.S - 1) * sg.n);
         }
 #pragma unroll
         for (int u = 0; u < 16; ++u) g += (s0 + u * grp < sg.S) ? v[u] : 0.f;
@@ -2155,7 +2272,7 @@ __device__ __forceinline__ void tr_opt_tile(const TrOptArgs& a, int b, float (*t
         g = red[e];
         for (int q = 1; q < grp; ++q) g += red[q * per + e];
       }
-      if (MODE == 0) {
+      if constexpr (MODE == 0) {
         if (valid) {
           if (a.g16) a.g16[i] = f2bf(g);
           else a.g[i] = g;
@@ -2165,22 +2282,7 @@ __device__ __forceinline__ void tr_opt_tile(const TrOptArgs& a, int b, float (*t
     } else {
       g = a.g16 ? bf2f(a.g16[i]) : a.g[i];
     }
-    const float t = static_cast<float>(a.step[0]);
-    const float gi = g * a.grad_scale + a.wd * p;
-    if (a.kind == 0) {
-      const float bc1 = 1.f - __powf(a.b1, t), bc2 = 1.f - __powf(a.b2, t);
-      m = a.b1 * m + (1.f - a.b1) * gi;
-      v = a.b2 * v + (1.f - a.b2) * gi * gi;
-      p -= a.lr * (m / bc1) / (sqrtf(v / bc2) + a.eps);
-    } else if (a.kind == 1) {
-      v += gi * gi;
-      p -= a.lr * gi / (sqrtf(v) + a.eps);
-    } else if (a.kind == 2) {
-      p -= a.lr * gi;
-    } else {
-      m = a.b1 * m + gi;
-      p -= a.lr * m;
-    }
+    tr_opt_update(a, g, p, m, v);
     if (valid) {
       a.p[i] = p;
       a.m[i] = m;
@@ -2192,19 +2294,69 @@ __device__ __forceinline__ void tr_opt_tile(const TrOptArgs& a, int b, float (*t
   if (sg.cols > 0 && sg.sh) {
     tile_s[tid >> 5][tid & 31] = p;
     __syncthreads();
-    const int r0 = r - (tid >> 5), c0 = c - (tid & 31);
-    if (tid < 32) {
-      const int row = tid >> 2, kc = (tid & 3) * 8;
-      float t8[8];
+    if (tid < 64) tr_opt_shadow(sg.sh, sg.shT, sg.rows, sg.cols, r - (tid >> 5), c - (tid & 31), tile_s, tid);
+  }
+}
+
+// every dW of the step in one launch and, fused, the optimizer in its trailing blocks (TrDwLaunch)
+__global__ __launch_bounds__(256, 2) void tr_dw_all_kernel(TrDwLaunch a) {
+  __shared__ __attribute__((aligned(16))) RouteLds gs;
+  __shared__ uint4_t lut[256];
+  const int b = blockIdx.x;
+  const bool pipe = a.route_impl == 2;  // that body fills the table itself, behind its first loads
+  if (!pipe && a.nroute > 0 && b < a.rwg[a.nroute]) {  // routed blocks: the fragment-spread table first
+    tr_spread_lut_init(lut);
+    __syncthreads();
+  }
+  if (pipe && a.nroute > 0 && b < a.rwg[a.nroute]) {
+    // one copy of the body for both routed problems: the problem is picked into registers
+    const bool second = b >= a.rwg[1];  // uniform
+    TrDwProb pr = a.route[0];
+    if (second) pr = a.route[1];
+    uint32_t* ready = a.fuse ? a.opt.sync + static_cast<int64_t>(second ? a.opt.cnt0[1] : a.opt.cnt0[0]) * kTrSyncLine : nullptr;
+    tr_dw_route_pipe_body(pr, second ? b - a.rwg[1] : b, gs, lut, second ? nullptr : a.prof, ready);
+  } else if (a.nroute > 0 && b < a.rwg[1]) {
+    tr_dw_route_body(a.route[0], b, gs, lut, a.prof,
+                     a.fuse ? a.opt.sync + static_cast<int64_t>(a.opt.cnt0[0]) * kTrSyncLine : nullptr);
+  } else if (a.nroute > 1 && b < a.rwg[2]) {
+    tr_dw_route_body(a.route[1], b - a.rwg[1], gs, lut, nullptr,
+                     a.fuse ? a.opt.sync + static_cast<int64_t>(a.opt.cnt0[1]) * kTrSyncLine : nullptr);
+  } else if (b < a.ndw) {
+    // the dW block count, not the grid's: trailing blocks do not move the stored-G blocks
+    const int r = a.rwg[a.nroute];
+    const int id = xcd_remap(b - r, a.ndw - r);
+    // constant indices only (no dynamic indexing of kernel arguments)
+    TrDwProb pr = a.plain.p[0];
+    TrFoldSeg fz = a.opt.fseg[0];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) t8[k] = tile_s[row][kc + k];
-      *reinterpret_cast<uint4_t*>(sg.sh + fm_off(r0 + row, c0 + kc, sg.cols)) = pack_bf16x8(t8);
-    } else if (tid < 64 && sg.shT) {
-      const int col = tid - 32;
-      float t8[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) t8[k] = tile_s[k][col];
-      *reinterpret_cast<uint4_t*>(sg.shT + fm_off(c0 + col, r0, sg.rows)) = pack_bf16x8(t8);
+    for (int i = 1; i < kTrMaxProbs; ++i)
+      if (a.plain.n > i && id >= a.plain.p[i].wg0) {
+        pr = a.plain.p[i];
+        fz = a.opt.fseg[i];
+      }
+    float* slots = reinterpret_cast<float*>(&gs[0][0][0]);
+    if (pr.F > 0) tr_dw_fold_body(pr, id - pr.wg0, slots, a.opt, fz, a.fuse != 0);  // uniform per block
+    else tr_dw_plain_body(pr, id - pr.wg0);
+  } else {
+    // Trailing optimizer blocks of a fused launch.  A tile block waits only for routed blocks,
+    // which have lower block ids and wait for nothing.  Workgroups are dispatched in id order,
+    // so by the time a trailing block is resident every one of its producers has been
+    // dispatched and runs to its end whatever the trailing blocks do: no cycle, no deadlock
+    // (the assumption of the decoupled look-back scan graph_build.hip relies on).  The blocks
+    // that wait for nothing come first, so they never queue behind pollers.
+    tr_opt_tile<2, true>(a.opt, b - a.ndw, reinterpret_cast<float(*)[33]>(&gs[0][0][0]));
+    // done ticket: taken by the polling lane behind its poll; the last of the launch zeroes the
+    // counters and the ticket, so a graph replay or a second launch starts from zero without a
+    // memset node.  Every other trailing block has finished polling by then, and a tile's
+    // counter reached S only after all its producers' adds.
+    if (threadIdx.x == 0) {
+      const uint32_t nt = static_cast<uint32_t>(gridDim.x) - static_cast<uint32_t>(a.ndw);
+      if (__hip_atomic_fetch_add(a.opt.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nt - 1u) {
+        for (int k = 2; k < a.opt.nsync; ++k)
+          __hip_atomic_store(a.opt.sync + static_cast<int64_t>(k) * kTrSyncLine, 0u, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(a.opt.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
   }
 }
@@ -2458,8 +2610,40 @@ hipError_t eh_tr_dw(TrDwLaunch* L, hipStream_t s) {
     p.wg0 = wg;
     wg += p.ntiles * p.S;
   }
-  const int total = L->rwg[L->nroute] + wg;
+  int total = L->rwg[L->nroute] + wg;
   if (total == 0) return hipSuccess;
+  L->ndw = total;
+  if (L->fuse) {
+    // the optimizer in the launch: every stored-G problem folded with a flat segment of its own,
+    // the trailing segments vectors first, then one weight segment per routed problem whose slabs
+    // are that problem's, and a hand-off line for the ticket, the status and every routed tile
+    TrDwOpt& o = L->opt;
+    if (L->fuse != 1 || !o.p || !o.m || !o.v || !o.step || !o.loss_acc || !o.loss_out || !o.head_part || o.nhead < 1 ||
+        !o.sync || o.timeout < 1 || o.nseg < 1 || o.nseg > kTrMaxSegs || o.rseg0 < 0 ||
+        o.rseg0 + L->nroute != o.nseg)
+      return hipErrorInvalidValue;
+    for (int i = 0; i < pr->n; ++i)
+      if (pr->p[i].F < 1 || o.fseg[i].off < 0 || o.fseg[i].off % 4 != 0 || (o.fseg[i].shT && !o.fseg[i].sh))
+        return hipErrorInvalidValue;
+    int blk = 0, line = 2;
+    for (int k = 0; k < o.nseg; ++k) {
+      const TrSeg& g = o.seg[k];
+      if (!g.part || g.S < 1 || g.blk0 != blk) return hipErrorInvalidValue;
+      if (k < o.rseg0) {
+        if (g.cols != 0 || g.sh || g.shT || g.sgrp != tr_seg_groups(g)) return hipErrorInvalidValue;
+      } else {
+        const TrDwProb& p = L->route[k - o.rseg0];
+        if (g.part != p.part || g.S != p.S || g.rows != p.P || g.cols != p.Q ||
+            static_cast<int64_t>(g.rows) * g.cols != g.n || (g.shT && !g.sh))
+          return hipErrorInvalidValue;
+        o.cnt0[k - o.rseg0] = line;
+        line += p.ntiles;
+      }
+      blk += tr_seg_blocks(g);
+    }
+    if (blk != o.nblk || line != o.nsync) return hipErrorInvalidValue;
+    total += blk;
+  }
   hipLaunchKernelGGL(tr_dw_all_kernel, dim3(static_cast<uint32_t>(total)), dim3(256), 0, s, *L);
   return hipGetLastError();
 }

@@ -261,8 +261,48 @@ struct TrOptArgs {
   int32_t opt_tpb;         //   with gather tiles: parameter tiles per block (fewer, longer blocks)
 };
 
+// The optimizer inside the dW launch (single-process step, plan key dw_opt_fuse): what tr_opt
+// mode 2 does, without a second launch.  Folded stored-G problems apply the update to their
+// 32x32 tile in the block that summed it (fseg: the flat segment of stored-G problem i).
+// Everything else runs in trailing blocks behind the dW blocks: first the segments that wait on
+// nothing (vectors; block 0 also reduces the head statistics), then one block per 8 x 32 tile of
+// each routed segment (seg[rseg0 + r] belongs to routed problem r), which waits for the S slabs
+// of the 64 x 128 routed tile it lies in.  No sampler and no gather arguments: the launch stays
+// well inside the kernel-argument limit.
+struct TrFoldSeg {
+  int64_t off;          // first flat element of the weight
+  uint16_t *sh, *shT;   // optional fm shadows
+};
+struct TrDwOpt {
+  float *p, *m, *v;
+  TrSeg seg[kTrMaxSegs];  // trailing segments, blk0 counted from the first trailing block
+  int32_t nseg, nblk;
+  int32_t rseg0;          // first routed segment of seg[] (== nseg: none)
+  TrFoldSeg fseg[kTrMaxProbs];
+  const int64_t* step;
+  float lr, b1, b2, eps, wd, grad_scale;
+  int32_t kind;
+  const float* head_part;
+  int32_t nhead;
+  float* loss_acc;
+  uint32_t* counts;
+  float* loss_out;
+  float* stat_f;
+  // hand-off state, plan-owned, zero between launches; 32 words (one 128-byte line) each:
+  // [0] done ticket, [1] status (kTrFuseTimeout), [2 + t] ready counter of routed tile t
+  uint32_t* sync;
+  int32_t nsync;          // lines in sync[]
+  int32_t cnt0[2];        // first counter line of routed problem r (filled by eh_tr_dw)
+  long long timeout;      // wall_clock64 ticks a tile block waits for its producers
+};
+constexpr int kTrSyncLine = 32;       // words per hand-off line
+constexpr uint32_t kTrFuseTimeout = 1u;
+// 12 ms of the 100 MHz wall clock: about 1000 x the 11.9 us the whole dW launch takes at the
+// headline shape (profiles/dw_opt_fuse/README.md)
+constexpr long long kTrFuseWaitTicks = 1200000;
+
 // one launch for every dW of the step: routed problems first (their blocks, S % 8 == 0),
-// then the stored-G problems grouped
+// then the stored-G problems grouped, then (fuse) the trailing optimizer blocks
 struct TrDwLaunch {
   TrDwProbs plain;
   TrDwProb route[2];
@@ -271,6 +311,9 @@ struct TrDwLaunch {
   int32_t route_impl;   // 2: build / load / multiply woven into one pipelined stage (the default),
                         // 0: one after the other (the equality baseline)
   long long* prof;      // optional [route blocks][8] wall-clock stamps (diagnostics)
+  int32_t ndw;          // dW blocks of the grid (filled by eh_tr_dw): the stored-G blocks' XCD mapping
+  int32_t fuse;         // 1: every stored-G problem is folded and opt describes the optimizer
+  TrDwOpt opt;
 };
 
 }  // namespace euler_hip
@@ -284,7 +327,7 @@ hipError_t eh_tr_fwd(const euler_hip::TrFwdArgs* a, int mode, int feat_fp32, int
 size_t eh_tr_gather32_lds(int D, int FL);
 hipError_t eh_tr_head(const euler_hip::TrHeadArgs* a, int64_t B, hipStream_t s);
 hipError_t eh_tr_bwd(const euler_hip::TrBwdArgs* a, hipStream_t s);
-// fills tiles / wg0 of every problem from P, Q, S, F before launching
+// fills tiles / wg0 of every problem from P, Q, S, F (and ndw, opt.cnt0) before launching
 hipError_t eh_tr_dw(euler_hip::TrDwLaunch* p, hipStream_t s);
 // mode 0: split-K reduce into g; 1: optimizer from g; 2: both fused (single process);
 // 3: shadows only (after an external parameter write).  Modes 1/2 also run a->nsample

@@ -112,6 +112,8 @@ class _Tower:
                  "gW0": self.gW0}
             if os.environ.get("EULER_AMD_DW_ROUTE_IMPL"):  # body of the routed W0 problem (0: the baseline)
                 d["dw_route_impl"] = int(os.environ["EULER_AMD_DW_ROUTE_IMPL"])
+            if os.environ.get("EULER_AMD_DW_OPT_FUSE"):  # checked; the tower's backward keeps its reduce launch
+                d["dw_opt_fuse"] = int(os.environ["EULER_AMD_DW_OPT_FUSE"])
             self._keep = d
             self.plan = hip().TowerPlan(d)
 
@@ -217,6 +219,8 @@ class UnsupSageTrainer:
             d["dw_fold"] = int(os.environ["EULER_AMD_DW_FOLD"])
         if os.environ.get("EULER_AMD_DW_ROUTE_IMPL"):
             d["dw_route_impl"] = int(os.environ["EULER_AMD_DW_ROUTE_IMPL"])
+        if os.environ.get("EULER_AMD_DW_OPT_FUSE"):  # 0: the optimizer keeps a launch of its own
+            d["dw_opt_fuse"] = int(os.environ["EULER_AMD_DW_OPT_FUSE"])
         self._pair_keep = d
         self.pair = hip().PairPlan(self.towers["gnn"].plan, self.towers["context_gnn"].plan, d)
         self.pair.opt(3)  # bf16 shadows of every weight
@@ -226,6 +230,9 @@ class UnsupSageTrainer:
         p.sample()
         p.fwd()
         p.head()
+        if grad_sync is None and p.fused():
+            p.dw(True, 1.0)  # the optimizer in the dW launch's trailing blocks
+            return self.loss_out
         p.dw()
         if grad_sync is None:
             p.opt(2)
@@ -526,6 +533,8 @@ class UnsupSageTrainer:
     def metric(self):
         """mean reciprocal rank of the positive since the last reset"""
         n = max(self.mrr_n_steps(), 1)
+        if self.pair is not None and self.pair.fuse_error():
+            raise RuntimeError("a fused dW + optimizer launch timed out waiting for its routed blocks")
         return float(self.mrr_sum.item()) / (n * self.B)
 
     def mrr_n_steps(self):

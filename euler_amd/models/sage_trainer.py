@@ -324,7 +324,7 @@ class SageTrainer:
              "lr": self.lr, "beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps,
              "weight_decay": self.wd, "opt_kind": _OPT_KIND[self.opt_name]}
         for key in ("EULER_AMD_DW_TARGET_WG", "EULER_AMD_DW_MIN_KPS", "EULER_AMD_DW_ROUTE_WG", "EULER_AMD_FWD_BM",
-                    "EULER_AMD_DW_ROUTE_IMPL", "EULER_AMD_DW_FOLD"):
+                    "EULER_AMD_DW_ROUTE_IMPL", "EULER_AMD_DW_FOLD", "EULER_AMD_DW_OPT_FUSE"):
             if os.environ.get(key):
                 d[key[len("EULER_AMD_"):].lower()] = int(os.environ[key])
         M_last = self.M[L - 1]
@@ -374,6 +374,8 @@ class SageTrainer:
         self._dw_all = list(range(self.plan.num_problems()))
         self._primed = False  # the sample buffers hold the batch of counter graph.rng[1]
         self.pipelined = bool(self.plan.pipeline_ok())
+        # the single-process step runs the optimizer inside the dW launch (plan key dw_opt_fuse)
+        self._fused = bool(self.plan.fused()) and not _SAMPLE_IN_OPT and not self.pipelined
         self._gathered = False  # A0_rows / A0_kt hold the layer-0 inputs of the sampled batch
 
     # ------------------------------------------------------------------ parameters / state
@@ -486,6 +488,21 @@ class SageTrainer:
             return [("all", 0, o[-1])]
         return [("head", o[self.L - 1], o[-1]), ("routed", 0, o[self.L - 1])]
 
+    def fused(self, grad_sync=None) -> bool:
+        """whether :meth:`step` with this ``grad_sync`` runs the split-K reduce and the optimizer
+        inside the dW launch (three launches) instead of an optimizer launch of its own"""
+        return self.on_gpu and self._fused and grad_sync is None
+
+    def fuse_error(self) -> int:
+        """0 unless a block of a fused dW launch gave up waiting for its producers (the step's
+        loss is NaN then); synchronises"""
+        return int(self.plan.fuse_error()) if self.on_gpu else 0
+
+    def _check_fuse(self):
+        if self.on_gpu and self._fused and self.plan.fuse_error():
+            raise RuntimeError("a fused dW + optimizer launch timed out waiting for its routed blocks: "
+                               "the parameters of that step are wrong")
+
     def step(self, grad_sync=None):
         """One training step.  ``grad_sync(bucket)`` (e.g. an in-place RCCL all-reduce)
         is called once per gradient bucket (:meth:`grad_buckets`, in that order) and
@@ -499,7 +516,9 @@ class SageTrainer:
 
         Single process: one stream, no forks (a hipGraph branch join costs more than the
         work it would overlap): fwd -> head -> [bwd] -> every dW in one launch ->
-        optimizer.  The head launch also carries the sampler of the NEXT step's batch in
+        optimizer; where :meth:`fused` holds, the optimizer runs in that dW launch (its fold
+        blocks and trailing blocks, plan key ``dw_opt_fuse``) and the step is three launches.
+        The head launch also carries the sampler of the NEXT step's batch in
         extra blocks, on the CUs the head's B/16 blocks leave idle (sampling reads only the
         graph and the RNG counter the forward advanced; the head reads the forward's copy
         of the roots), so the sampler's dependent-load chain is off the critical path.
@@ -522,7 +541,9 @@ class SageTrainer:
         p.head(None, not smp_opt)
         p.bwd()
         gat = self.pipelined  # this launch gathers the batch the head just sampled
-        if grad_sync is None:
+        if grad_sync is None and self._fused:
+            p.dw(self._dw_all, None, True, 1.0)  # the optimizer in the launch's trailing blocks
+        elif grad_sync is None:
             p.dw(self._dw_all)
             p.opt(2, 1.0, smp_opt, gat)
         elif len(self.grad_buckets()) == 1:
@@ -567,7 +588,10 @@ class SageTrainer:
                ("head+sample", lambda: p.head(None, True))]
         if self.L == 3:
             out.append(("bwd", p.bwd))
-        out += [("dw", lambda: p.dw(self._dw_all)), ("opt", lambda: p.opt(2))]
+        if self._fused:
+            out.append(("dw+opt", lambda: p.dw(self._dw_all, None, True, 1.0)))
+        else:
+            out += [("dw", lambda: p.dw(self._dw_all)), ("opt", lambda: p.opt(2))]
         if self.pipelined:
             out += [("opt+gather", lambda: p.opt(2, 1.0, False, True)), ("fwd_gemm", lambda: p.fwd(None, True))]
         return out
@@ -675,6 +699,7 @@ class SageTrainer:
     def metric(self) -> float:
         """streaming micro-F1 (threshold 0.5) since the last :meth:`reset_metric`
         (reference metrics.f1_score)"""
+        self._check_fuse()
         tp, fp, fn = (self.counts.tolist() if self.on_gpu else self._cpu_counts)
         return 2.0 * tp / max(2.0 * tp + fp + fn, 1e-12)
 

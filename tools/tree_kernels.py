@@ -61,6 +61,10 @@ def main():
     res["dw_splits"] = p.splits()
     res["dw_folds"] = p.folds()
     res["route_profile"] = route_profile(tr)
+    # the routed blocks inside the step's own dW launch (every problem; with the optimizer's
+    # trailing blocks when the plan is fused)
+    res["fused"] = bool(tr.fused())
+    res["route_profile_step"] = route_profile(tr, whole=True)
     tr.capture(steps=4)
     res["graph_step"] = round(timeit(lambda: tr.replay(1), args.reps), 2)
     res["graph_step_x4"] = round(timeit(lambda: tr.replay_steps(4), args.reps) / 4, 2)  # per step
@@ -100,8 +104,9 @@ def main():
               "span", round(float(t[:, 7].max() - t0), 2), "start skew", round(float(t[:, 0].max() - t0), 2))
 
 
-def route_profile(tr, reps=3):
-    """wall-clock stamps of the routed dW blocks (problem 0): start, progress points, end"""
+def route_profile(tr, reps=3, whole=False):
+    """wall-clock stamps of the routed dW blocks (problem 0): start, progress points, end;
+    whole: in the launch of all problems as the step issues it, not alone"""
     p = tr.plan
     nb = p.route_blocks(0)
     if nb == 0:
@@ -109,7 +114,12 @@ def route_profile(tr, reps=3):
     prof = torch.zeros(nb * 8, dtype=torch.int64, device=tr.device)
     for _ in range(reps):
         prof.zero_()
-        p.dw([0], prof)
+        if whole and tr.fused():
+            p.dw(tr._dw_all, prof, True, 1.0)
+        elif whole:
+            p.dw(tr._dw_all, prof)
+        else:
+            p.dw([0], prof)
     torch.cuda.synchronize()
     t = prof.view(-1, 8).cpu().double() / 100.0  # wall_clock64 = 100 MHz
     t0 = t[:, 0].min()
