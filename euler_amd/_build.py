@@ -192,6 +192,24 @@ def build_selftest(sanitize: str = "thread", max_workers: int = 8) -> str:
     return out
 
 
+def build_plan_selftest() -> str:
+    """Self-test binary of the dW / optimizer planner (csrc/tests/tree_plan_selftest.cc over
+    csrc/hip/tree_plan.h) under ASAN + UBSan.  Host code only: the HIP headers are read for
+    their types, nothing of HIP is called or linked.  Returns the binary path (mtime-cached)."""
+    objdir = os.path.join(BUILD, "selftest_address")
+    os.makedirs(objdir, exist_ok=True)
+    out = os.path.join(objdir, "tree_plan_selftest")
+    src = os.path.join(CSRC, "tests", "tree_plan_selftest.cc")
+    hdir = os.path.join(CSRC, "hip")
+    deps = [src, os.path.join(hdir, "tree_plan.h"), os.path.join(hdir, "tree_args.h"), __file__]
+    if not os.path.exists(out) or os.path.getmtime(out) < _newest(deps):
+        rocm_inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
+        _run(["g++", "-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer", "-Wall"] + _SANITIZERS["address"] +
+             ["-D__HIP_PLATFORM_AMD__=1", "-I" + CSRC, "-I" + rocm_inc, src, "-o", out])
+        _log("linked " + os.path.relpath(out, REPO))
+    return out
+
+
 # ----------------------------------------------------------------------------
 # HIP kernels (gfx950) + torch binding
 # ----------------------------------------------------------------------------

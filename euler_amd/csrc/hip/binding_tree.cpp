@@ -9,7 +9,7 @@
 #include <cstdlib>
 
 #include "hip/binding_util.h"
-#include "hip/tree_args.h"
+#include "hip/tree_plan.h"
 
 using namespace euler_bind;
 using namespace euler_hip;
@@ -69,17 +69,6 @@ void fill_graph_tree(PlanDict& pd, TrGraph& g, TrTree& tr, int64_t F1, int64_t F
   tr.m2 = m2;
 }
 
-// split plan of a stored-G dW problem from the keys every plan shares: dw_target_wg (512),
-// dw_min_kps (4), dw_fold (1; 0 = every slab goes through `part`)
-void plan_stored(const PlanDict& pd, TrDwProb& p) {
-  const int64_t target = pd.has("dw_target_wg") ? pd.geti("dw_target_wg") : 512;
-  const int64_t minkps = pd.has("dw_min_kps") ? pd.geti("dw_min_kps") : 4;
-  const int64_t fold = pd.has("dw_fold") ? pd.geti("dw_fold") : 1;
-  TORCH_CHECK(target >= 1 && minkps >= 1 && (fold == 0 || fold == 1), pd.name(),
-              ": dw_target_wg / dw_min_kps must be positive, dw_fold 0 or 1");
-  tr_plan_stored(p, target, minkps, fold == 1);
-}
-
 // body of the routed dW problems, the key every plan shares: dw_route_impl (2: the pipelined
 // stage loop; 0: build, load and multiply one after the other, the equality baseline; 1 was a
 // body that built G per wave in registers: slower than both, profiles/dw_route_pipe/README.md)
@@ -98,83 +87,213 @@ bool plan_fuse_key(const PlanDict& pd) {
   return f == 1;
 }
 
-// TrDwOpt of dW launch L from the optimizer arguments o of tr_opt mode 2: each flat segment is
-// found by the `part` slabs it sums.  Stored-G problems must be folded (their blocks update the
-// tile themselves); vector segments, then the routed problems' segments in the launch's order,
-// go to trailing blocks.  False: this launch cannot carry the optimizer (an unfolded stored-G
-// problem, or a problem or segment without its counterpart).  sync_lines: hand-off lines needed.
-bool fill_dw_opt(const TrDwLaunch& L, const TrOptArgs& o, TrDwOpt& f, int64_t& sync_lines) {
-  f = TrDwOpt{};
-  const TrSeg* rseg[2] = {nullptr, nullptr};
-  bool pseg[kTrMaxProbs] = {};
-  int nvec = 0;
-  for (int k = 0; k < o.nseg; ++k) {
-    const TrSeg& g = o.seg[k];
-    if (g.cols == 0) {
-      f.seg[nvec++] = g;
-      continue;
-    }
-    bool found = false;
-    for (int r = 0; r < L.nroute && !found; ++r)
-      if (L.route[r].part == g.part && !rseg[r]) {
-        rseg[r] = &g;
-        found = true;
-      }
-    for (int i = 0; i < L.plain.n && !found; ++i) {
-      const TrDwProb& p = L.plain.p[i];
-      if (p.part != g.part || pseg[i]) continue;
-      if (p.F < 1 || g.S != 1 || g.rows != p.P || g.cols != p.Q || g.off % 4 != 0) return false;
-      f.fseg[i] = TrFoldSeg{g.off, g.sh, g.shT};
-      pseg[i] = true;
-      found = true;
-    }
-    if (!found) return false;
-  }
-  for (int i = 0; i < L.plain.n; ++i)
-    if (!pseg[i]) return false;
-  f.rseg0 = nvec;
-  f.nseg = nvec + L.nroute;
-  if (f.nseg < 1 || f.nseg > kTrMaxSegs) return false;
-  sync_lines = 2;
-  for (int r = 0; r < L.nroute; ++r) {
-    if (!rseg[r]) return false;
-    f.seg[nvec + r] = *rseg[r];
-    const TrDwProb& p = L.route[r];
-    sync_lines += static_cast<int64_t>(p.P / 64) * ((p.Q + 127) / 128);
-  }
-  int blk = 0;
-  for (int k = 0; k < f.nseg; ++k) {
-    f.seg[k].blk0 = blk;
-    blk += tr_seg_prepare(f.seg[k]);
-  }
-  f.nblk = blk;
-  f.p = o.p;
-  f.m = o.m;
-  f.v = o.v;
-  f.step = o.step;
-  f.lr = o.lr;
-  f.b1 = o.b1;
-  f.b2 = o.b2;
-  f.eps = o.eps;
-  f.wd = o.wd;
-  f.grad_scale = o.grad_scale;
-  f.kind = o.kind;
-  f.head_part = o.head_part;
-  f.nhead = o.nhead;
-  f.loss_acc = o.loss_acc;
-  f.counts = o.counts;
-  f.loss_out = o.loss_out;
-  f.stat_f = o.stat_f;
-  f.nsync = static_cast<int32_t>(sync_lines);
-  f.timeout = kTrFuseWaitTicks;
-  return o.nhead > 0;
-}
+// The dW problems of a plan, the optimizer over its flat parameters and, where the plan fuses,
+// the optimizer inside the dW launch of every problem: its TrDwOpt and hand-off state are built
+// once (try_fuse), a fused launch patches only lr, grad_scale and prof.  All geometry comes from
+// tree_plan.h.
+class DwPlan {
+ public:
+  explicit DwPlan(PlanDict& pd) : pd_(pd), route_impl_(plan_route_impl(pd)), fuse_key_(plan_fuse_key(pd)) {}
 
-// the status word of a plan's hand-off state (0: every wait of every fused launch so far was
-// met); synchronises
-int64_t fuse_status(const torch::Tensor& sync) {
-  return sync.defined() ? sync[kTrSyncLine].item<int64_t>() : 0;
-}
+  std::vector<TrDwProb> probs;  // in the plan's order: the indices of launch() and splits()
+  TrOptArgs opt{};              // tr_opt over the flat parameters
+
+  // dW = G^T X [P][Q] over M rows, with its split plan and plan-owned partials.  dA: routed (G
+  // built from the parent gradient through the tree and the ReLU bits), S from dw_route_wg
+  // (256); else stored-G, from dw_target_wg (512), dw_min_kps (4) and dw_fold (1; 0 = every
+  // slab goes through `part`)
+  const TrDwProb& add(int64_t P, int64_t Q, int64_t M, const uint16_t* G, const uint16_t* X, const float* dA,
+                      const uint32_t* mask, int64_t logPg, int64_t Fg, int64_t self) {
+    TORCH_CHECK(M % 32 == 0 && P % 32 == 0 && Q % 32 == 0, pd_.name(), ": dW problem shapes");
+    TrDwProb p{};
+    p.P = static_cast<int32_t>(P);
+    p.Q = static_cast<int32_t>(Q);
+    p.MB = static_cast<int32_t>(M / 32);
+    if (dA) {
+      TORCH_CHECK(tr_plan_routed(p, pd_.has("dw_route_wg") ? pd_.geti("dw_route_wg") : 256), pd_.name(),
+                  ": routed dW needs P % 64 == 0 and a positive dw_route_wg");
+      p.route = 1;
+      p.dA = dA;
+      p.mask = mask;
+      p.logPg = static_cast<int32_t>(logPg);
+      p.Fg = static_cast<int32_t>(Fg);
+      p.include_self = static_cast<int32_t>(self);
+      p.inv = 1.f / static_cast<float>(Fg + self);
+    } else {
+      const int64_t target = pd_.has("dw_target_wg") ? pd_.geti("dw_target_wg") : 512;
+      const int64_t minkps = pd_.has("dw_min_kps") ? pd_.geti("dw_min_kps") : 4;
+      const int64_t fold = pd_.has("dw_fold") ? pd_.geti("dw_fold") : 1;
+      TORCH_CHECK(target >= 1 && minkps >= 1 && (fold == 0 || fold == 1), pd_.name(),
+                  ": dw_target_wg / dw_min_kps must be positive, dw_fold 0 or 1");
+      tr_plan_stored(p, target, minkps, fold == 1);
+    }
+    p.part = pd_.zeros_ptr<float>(static_cast<int64_t>(p.S) * P * Q, torch::kFloat32);
+    p.G = G;
+    p.X = X;
+    probs.push_back(p);
+    return probs.back();
+  }
+
+  // the next flat segment, at offset off: the weight of problem p (sums its slabs; optional fm
+  // shadows), or a vector of n elements summed from S partials
+  void add_seg(int64_t off, const TrDwProb& p, const uint16_t* sh, const uint16_t* shT) {
+    TrSeg& g = next_seg();
+    g.off = off;
+    g.n = static_cast<int64_t>(p.P) * p.Q;
+    g.part = p.part;
+    g.S = p.S;
+    g.rows = p.P;
+    g.cols = p.Q;
+    g.sh = const_cast<uint16_t*>(sh);
+    g.shT = const_cast<uint16_t*>(shT);
+  }
+  void add_vec_seg(int64_t off, int64_t n, const float* part, int64_t S) {
+    TrSeg& g = next_seg();
+    g.off = off;
+    g.n = n;
+    g.part = part;
+    g.S = static_cast<int32_t>(S);
+    g.rows = 1;
+  }
+  void layout_segs() {
+    opt.nblk = tr_seg_layout(opt.seg, opt.nseg, true);
+    TORCH_CHECK(opt.nblk >= 1, pd_.name(), ": weight segments need rows % 8, cols % 32");
+  }
+
+  // state, hyper-parameters and loss hand-off of the optimizer from the keys every optimizing
+  // plan shares: flat (n parameters, then padding), grad, m, v, step, lr, beta1, beta2, eps,
+  // weight_decay, opt_kind, loss_acc, loss_out and the head's second statistic (rank_stat:
+  // mrr_sum, the reciprocal ranks of a pair model; else counts: tp, fp, fn)
+  void fill_opt(int64_t n, const float* head_part, int64_t nhead, bool rank_stat) {
+    torch::Tensor flat = pd_.T("flat");
+    pd_.need(flat, torch::kFloat32, -1, "flat");
+    const int64_t nbuf = flat.numel();
+    TORCH_CHECK(n <= nbuf, pd_.name(), ": offsets must lie inside the flat buffer");
+    opt.n = n;
+    opt.p = flat.data_ptr<float>();
+    opt.g = pd_.f32("grad", nbuf);
+    opt.m = pd_.f32("m", nbuf);
+    opt.v = pd_.f32("v", nbuf);
+    opt.step = pd_.ptr<int64_t>("step", torch::kInt64, 1);
+    opt.lr = static_cast<float>(pd_.getf("lr"));
+    opt.b1 = static_cast<float>(pd_.getf("beta1"));
+    opt.b2 = static_cast<float>(pd_.getf("beta2"));
+    opt.eps = static_cast<float>(pd_.getf("eps"));
+    opt.wd = static_cast<float>(pd_.getf("weight_decay"));
+    opt.grad_scale = 1.f;
+    opt.kind = static_cast<int32_t>(pd_.geti("opt_kind"));
+    opt.head_part = head_part;
+    opt.nhead = static_cast<int32_t>(nhead);
+    opt.loss_acc = pd_.f32("loss_acc", 1);
+    opt.loss_out = pd_.f32("loss_out", 1);
+    if (rank_stat) opt.stat_f = pd_.f32("mrr_sum", 1);
+    else opt.counts = reinterpret_cast<uint32_t*>(pd_.i32("counts", 3));
+  }
+
+  // plan key dw_opt_fuse: the launch of every problem carries the optimizer, where the plan
+  // allows it and tr_dw_fuse finds a place for every segment
+  void try_fuse(bool allowed) {
+    TrDwGrid grid;
+    TrDwLaunch L = launch_of(all(), false, grid);
+    if (!fuse_key_ || !allowed || !tr_dw_fuse(L, opt, fopt_)) return;
+    sync_ = pd_.zeros(static_cast<int64_t>(fopt_.nsync) * kTrSyncLine, torch::kInt32);
+    fopt_.sync = reinterpret_cast<uint32_t*>(sync_.data_ptr<int32_t>());
+    fused_ = true;
+  }
+  bool fused() const { return fused_; }
+  // the status word of the hand-off state (0: every wait of every fused launch so far was met);
+  // synchronises
+  int64_t fuse_error() const { return sync_.defined() ? sync_[kTrSyncLine].item<int64_t>() : 0; }
+
+  std::vector<int64_t> all() const {
+    std::vector<int64_t> w(probs.size());
+    for (size_t i = 0; i < w.size(); ++i) w[i] = static_cast<int64_t>(i);
+    return w;
+  }
+
+  // dW of the given problems, one launch: routed problems first, the others grouped.  fuse (a
+  // fused() plan, every problem in the plan's order): the launch also runs the optimizer, what
+  // tr_opt mode 2 with grad_scale would do after it
+  void launch(const std::vector<int64_t>& which, c10::optional<torch::Tensor> prof, bool fuse, double grad_scale) {
+    const c10::DeviceGuard g(pd_.device());
+    TrDwGrid grid;
+    TrDwLaunch L = launch_of(which, fuse, grid);
+    if (fuse) L.opt.grad_scale = static_cast<float>(grad_scale);
+    if (prof.has_value()) {
+      pd_.need(*prof, torch::kInt64, -1, "prof");
+      L.prof = reinterpret_cast<long long*>(prof->data_ptr<int64_t>());
+    }
+    tree_ok(eh_tr_dw(&L, cur_stream()), fuse ? "tr_dw+opt" : "tr_dw");
+  }
+  // workgroups of the launch of the given problems (fuse: with its trailing optimizer blocks)
+  int64_t blocks(const std::vector<int64_t>& which, bool fuse) const {
+    TrDwGrid grid;
+    launch_of(which, fuse, grid);
+    return grid.ndw + grid.ntrail;
+  }
+  std::vector<int64_t> splits() const {
+    std::vector<int64_t> s;
+    for (const auto& p : probs) s.push_back(p.S);
+    return s;
+  }
+  // slabs each problem sums inside its blocks (0: none, its S slabs go through `part`)
+  std::vector<int64_t> folds() const {
+    std::vector<int64_t> f;
+    for (const auto& p : probs) f.push_back(p.F);
+    return f;
+  }
+  void set_lr(double lr) { opt.lr = static_cast<float>(lr); }
+  // the flat fp32 gradient the reduce writes and the optimizer reads (e.g. a view of the xGMI
+  // all-reduce's IPC input region, so the all-reduce runs in place there); exact: of opt.n
+  // elements, else at least as many
+  void set_grad(torch::Tensor g, bool exact) {
+    pd_.need(g, torch::kFloat32, exact ? opt.n : -1, "grad");
+    TORCH_CHECK(g.numel() >= opt.n, "grad has ", g.numel(), " elements, fewer than the ", opt.n, " parameters");
+    grad_ = g;
+    opt.g = g.data_ptr<float>();
+  }
+
+ private:
+  PlanDict& pd_;
+  int route_impl_;
+  bool fuse_key_, fused_ = false;
+  TrDwOpt fopt_{};      // the optimizer of the fused launch of all(); lr follows opt.lr
+  torch::Tensor sync_;  // its hand-off state (TrDwOpt::sync)
+  torch::Tensor grad_;
+
+  TrSeg& next_seg() {
+    TORCH_CHECK(opt.nseg < kTrMaxSegs, pd_.name(), ": too many optimizer segments");
+    return opt.seg[opt.nseg++] = TrSeg{};
+  }
+
+  // the laid-out launch of the given problems
+  TrDwLaunch launch_of(const std::vector<int64_t>& which, bool fuse, TrDwGrid& grid) const {
+    TrDwLaunch L{};
+    L.route_impl = route_impl_;
+    bool every = which.size() == probs.size();
+    for (size_t k = 0; k < which.size(); ++k) {
+      const int64_t i = which[k];
+      TORCH_CHECK(i >= 0 && i < (int64_t)probs.size(), "dw: problem index out of range");
+      every = every && i == (int64_t)k;
+      if (probs[i].route) {
+        TORCH_CHECK(L.nroute < 2, "dw: at most two routed problems per launch");
+        L.route[L.nroute++] = probs[i];
+      } else {
+        TORCH_CHECK(L.plain.n < kTrMaxProbs, "dw: too many problems");
+        L.plain.p[L.plain.n++] = probs[i];
+      }
+    }
+    if (fuse) {
+      TORCH_CHECK(fused_ && every, pd_.name(),
+                  ": the optimizer runs in the dW launch of every problem, in the plan's order, of a fused() plan only");
+      L.opt = fopt_;
+      L.opt.lr = opt.lr;
+      L.fuse = 1;
+    }
+    TORCH_CHECK(tr_dw_layout(L, grid), pd_.name(), ": the dW launch is not one the kernel takes");
+    return L;
+  }
+};
 
 class TreePlan : private PlanDict {
  public:
@@ -202,7 +321,6 @@ class TreePlan : private PlanDict {
     M_.assign(L_, 0);
     M_[0] = B_;
     for (int k = 1; k < L_; ++k) M_[k] = M_[k - 1] << logP_[k];
-    route_impl_ = plan_route_impl(*this);
     fill_graph_tree(*this, graph_, tree_, L_ > 1 ? F_[1] : 0, L_ > 2 ? F_[2] : 0, L_ > 1 ? logP_[1] : 0,
                     L_ > 2 ? logP_[2] : 0, static_cast<uint32_t>(masks_[1]),
                     L_ > 2 ? static_cast<uint32_t>(masks_[2]) : 0u);
@@ -211,19 +329,13 @@ class TreePlan : private PlanDict {
     build_head();
     build_dw();
     build_opt();
-    // the optimizer in the dW launch of all problems (fill_dw_opt), unless the step is pipelined
-    // (its optimizer launch carries the next batch's gather)
-    TrDwLaunch L = launch_of(all_problems());
-    TrDwOpt f;
-    int64_t lines = 0;
-    if (plan_fuse_key(*this) && !pipeline_ok() && fill_dw_opt(L, opt_, f, lines)) {
-      fused_ = true;
-      sync_ = zeros(lines * kTrSyncLine, torch::kInt32);
-    }
+    // the optimizer in the dW launch of all problems, unless the step is pipelined (its
+    // optimizer launch carries the next batch's gather)
+    dw_.try_fuse(!pipeline_ok());
   }
 
-  bool fused() const { return fused_; }
-  int64_t fuse_error() const { return fuse_status(sync_); }
+  bool fused() const { return dw_.fused(); }
+  int64_t fuse_error() const { return dw_.fuse_error(); }
 
   void sample() {
     const c10::DeviceGuard g(device());
@@ -265,75 +377,17 @@ class TreePlan : private PlanDict {
     tree_ok(eh_tr_bwd(&bwd1_, cur_stream()), "tr_bwd");
   }
 
-  // dW of the given problems, one launch: routed problems first, the others grouped.
-  // fuse (a fused() plan, every problem): the launch also runs the optimizer, what opt(2,
-  // grad_scale) would do after it
+  // DwPlan::launch; fuse: what opt(2, grad_scale) would do after it runs in the launch
   void dw(std::vector<int64_t> which, c10::optional<torch::Tensor> prof, bool fuse, double grad_scale) {
-    const c10::DeviceGuard g(device());
-    TrDwLaunch L = launch_of(which);
-    if (prof.has_value()) {
-      need(*prof, torch::kInt64, -1, "prof");
-      L.prof = reinterpret_cast<long long*>(prof->data_ptr<int64_t>());
-    }
-    if (fuse) {
-      TORCH_CHECK(fused_ && L.nroute + L.plain.n == (int)probs_.size(),
-                  "dw: the optimizer runs in the dW launch of every problem of a fused() plan only");
-      TrOptArgs o = opt_;
-      o.grad_scale = static_cast<float>(grad_scale);
-      int64_t lines = 0;
-      TORCH_CHECK(fill_dw_opt(L, o, L.opt, lines) && lines * kTrSyncLine == sync_.numel(), "dw: fused plan changed");
-      L.opt.sync = reinterpret_cast<uint32_t*>(sync_.data_ptr<int32_t>());
-      L.fuse = 1;
-    }
-    if (L.nroute == 0 && L.plain.n == 0) return;
-    tree_ok(eh_tr_dw(&L, cur_stream()), fuse ? "tr_dw+opt" : "tr_dw");
+    dw_.launch(which, prof, fuse, grad_scale);
   }
-
   // workgroups of the dW launch of every problem (fuse: with its trailing optimizer blocks)
-  int64_t dw_blocks(bool fuse) const {
-    TORCH_CHECK(!fuse || fused_, "dw_blocks: the plan is not fused()");
-    int64_t n = 0;
-    for (size_t i = 0; i < probs_.size(); ++i) {
-      const TrDwProb& p = probs_[i];
-      if (p.route) n += route_blocks(static_cast<int64_t>(i));
-      else if (p.F > 0) n += static_cast<int64_t>(p.P / 32) * (p.Q / 32);
-      else n += static_cast<int64_t>((p.P + 63) / 64) * ((p.Q + 63) / 64) * p.S;
-    }
-    if (fuse) {
-      TrDwOpt f;
-      int64_t lines = 0;
-      TORCH_CHECK(fill_dw_opt(launch_of(all_problems()), opt_, f, lines), "dw_blocks: fused plan changed");
-      n += f.nblk;
-    }
-    return n;
-  }
-
-  std::vector<int64_t> all_problems() const {
-    std::vector<int64_t> w(probs_.size());
-    for (size_t i = 0; i < w.size(); ++i) w[i] = static_cast<int64_t>(i);
-    return w;
-  }
-
-  TrDwLaunch launch_of(const std::vector<int64_t>& which) const {
-    TrDwLaunch L{};
-    L.route_impl = route_impl_;
-    for (int64_t i : which) {
-      TORCH_CHECK(i >= 0 && i < (int64_t)probs_.size(), "dw: problem index out of range");
-      if (probs_[i].route) {
-        TORCH_CHECK(L.nroute < 2, "dw: at most two routed problems per launch");
-        L.route[L.nroute++] = probs_[i];
-      } else {
-        TORCH_CHECK(L.plain.n < kTrMaxProbs, "dw: too many problems");
-        L.plain.p[L.plain.n++] = probs_[i];
-      }
-    }
-    return L;
-  }
+  int64_t dw_blocks(bool fuse) const { return dw_.blocks(dw_.all(), fuse); }
 
   std::vector<int64_t> problems(bool route) const {
     std::vector<int64_t> out;
-    for (size_t i = 0; i < probs_.size(); ++i)
-      if (static_cast<bool>(probs_[i].route) == route) out.push_back(static_cast<int64_t>(i));
+    for (size_t i = 0; i < dw_.probs.size(); ++i)
+      if (static_cast<bool>(dw_.probs[i].route) == route) out.push_back(static_cast<int64_t>(i));
     return out;
   }
 
@@ -344,7 +398,7 @@ class TreePlan : private PlanDict {
   void opt(int64_t mode, double grad_scale, bool with_sample, bool with_gather) {
     const c10::DeviceGuard g(device());
     TORCH_CHECK(!with_gather || pipeline_ok(), "TreePlan: no pipelined gather for this plan");
-    TrOptArgs a = opt_;
+    TrOptArgs a = dw_.opt;
     a.grad_scale = static_cast<float>(grad_scale);
     if (!with_sample) a.nsample = 0;
     if (with_gather) {
@@ -377,66 +431,43 @@ class TreePlan : private PlanDict {
   // head_stats: this launch also reduces the head's loss / F1 partials
   void opt_segments(int64_t mode, std::vector<int64_t> segs, bool head_stats) {
     TORCH_CHECK(mode == 0, "opt_segments: only the reduce (mode 0) runs on a segment subset");
-    TORCH_CHECK(!segs.empty() && (int64_t)segs.size() <= opt_.nseg, "opt_segments: bad segment list");
+    TORCH_CHECK(!segs.empty() && (int64_t)segs.size() <= dw_.opt.nseg, "opt_segments: bad segment list");
     const c10::DeviceGuard g(device());
-    TrOptArgs a = opt_;
-    int blk = 0, n = 0;
+    TrOptArgs a = dw_.opt;
+    a.nseg = 0;
     for (int64_t k : segs) {
-      TORCH_CHECK(k >= 0 && k < opt_.nseg, "opt_segments: segment index out of range");
-      TrSeg s = opt_.seg[k];
-      s.blk0 = blk;
-      blk += tr_seg_prepare(s);
-      a.seg[n++] = s;
+      TORCH_CHECK(k >= 0 && k < dw_.opt.nseg, "opt_segments: segment index out of range");
+      a.seg[a.nseg++] = dw_.opt.seg[k];
     }
-    a.nseg = n;
-    a.nblk = blk;
+    a.nblk = tr_seg_layout(a.seg, a.nseg, true);
     a.nsample = 0;
     if (!head_stats) a.nhead = 0;
     tree_ok(eh_tr_opt(&a, 0, cur_stream()), "tr_opt(segments)");
   }
 
   int64_t fwd_blocks() const { return fwd0_.M / bm0_; }
-  void set_lr(double lr) { opt_.lr = static_cast<float>(lr); }
+  void set_lr(double lr) { dw_.set_lr(lr); }
+  void set_grad(torch::Tensor g) { dw_.set_grad(g, true); }
   // bf16 gradient buffer for the data-parallel hand-off (None: fp32 grad)
-  // the flat fp32 gradient the reduce launch writes and the optimizer reads (e.g. a view of
-  // the xGMI all-reduce's IPC input region, so the all-reduce runs in place there)
-  void set_grad(torch::Tensor g) {
-    need(g, torch::kFloat32, opt_.n, "grad");
-    grad_ = g;
-    opt_.g = g.data_ptr<float>();
-  }
   void set_grad16(c10::optional<torch::Tensor> g16) {
     if (!g16.has_value()) {
-      opt_.g16 = nullptr;
+      dw_.opt.g16 = nullptr;
       g16_ = torch::Tensor();
       return;
     }
-    need(*g16, torch::kBFloat16, opt_.n, "grad16");
+    need(*g16, torch::kBFloat16, dw_.opt.n, "grad16");
     g16_ = *g16;
-    opt_.g16 = reinterpret_cast<uint16_t*>(g16_.data_ptr());
+    dw_.opt.g16 = reinterpret_cast<uint16_t*>(g16_.data_ptr());
   }
-  int64_t num_problems() const { return (int64_t)probs_.size(); }
+  int64_t num_problems() const { return (int64_t)dw_.probs.size(); }
   // blocks of the routed problem i in a dw launch (the prof rows it stamps)
-  int64_t route_blocks(int64_t i) const {
-    const TrDwProb& p = probs_.at(i);
-    return p.route ? (int64_t)(p.P / 64) * ((p.Q + 127) / 128) * p.S : 0;
-  }
-  std::vector<int64_t> splits() const {
-    std::vector<int64_t> s;
-    for (const auto& p : probs_) s.push_back(p.S);
-    return s;
-  }
-  // slabs each problem sums inside its blocks (0: none, its S slabs go through `part`)
-  std::vector<int64_t> folds() const {
-    std::vector<int64_t> f;
-    for (const auto& p : probs_) f.push_back(p.F);
-    return f;
-  }
+  int64_t route_blocks(int64_t i) const { return dw_.probs.at(i).route ? dw_.blocks({i}, false) : 0; }
+  std::vector<int64_t> splits() const { return dw_.splits(); }
+  std::vector<int64_t> folds() const { return dw_.folds(); }
 
  private:
   int L_, B_, D_, E_, C_, C_real_, self_;
   int feat_fp32_ = 0, bm0_ = 32, bm1_ = 32;
-  int route_impl_ = 2;  // EULER_AMD_DW_ROUTE_IMPL / plan key dw_route_impl (plan_route_impl)
   bool cached_ = false;
   std::vector<int64_t> F_, logP_, masks_, dims_, M_;
   TrGraph graph_{};
@@ -445,12 +476,9 @@ class TreePlan : private PlanDict {
   TrFwdArgs fwd0_{}, fwd1_{};
   TrHeadArgs head_{};
   TrBwdArgs bwd1_{};
-  std::vector<TrDwProb> probs_;
+  DwPlan dw_{*this};  // conv layers 0..L-1, then fc and out_fc
   torch::Tensor roots_cur_;  // the forward's copy of the batch's roots (read by the head)
-  TrOptArgs opt_{};
-  torch::Tensor g16_, grad_;
-  bool fused_ = false;  // plan key dw_opt_fuse, where the launch of all problems can carry the optimizer
-  torch::Tensor sync_;  // hand-off state of the fused launch (TrDwOpt::sync)
+  torch::Tensor g16_;
 
   int64_t Hin(int k) const { return k == 0 ? D_ : dims_[k - 1]; }
 
@@ -622,136 +650,52 @@ class TreePlan : private PlanDict {
     }
   }
 
-  // split-K plan.  Stored-G problems: ~target workgroups of 64x64 tiles, at least min_kps
-  // 32-row k-blocks per split.  Routed problems: 64x128 tiles, S a multiple of 8 (XCD
-  // mapping) near route_target workgroups.
-  void plan_splits(TrDwProb& p, bool route) const {
-    const int64_t MB = p.MB;
-    if (route) {
-      const int64_t tiles = (p.P / 64) * ((p.Q + 127) / 128);
-      const int64_t target = has("dw_route_wg") ? geti("dw_route_wg") : 256;
-      int64_t S = (target + tiles - 1) / tiles;
-      S = (S + 7) / 8 * 8;
-      if (S > (MB + 7) / 8 * 8) S = (MB + 7) / 8 * 8;
-      p.kps = static_cast<int32_t>((MB + S - 1) / S);
-      p.S = static_cast<int32_t>(S);  // >= ceil(MB / kps); trailing splits may be empty
-      return;
-    }
-    plan_stored(*this, p);
-  }
-
-  void add_prob(const std::string& /*name*/, int64_t P, int64_t Q, int64_t M, const uint16_t* G, const uint16_t* X,
-                const float* dA, const uint32_t* mask, int logPg, int Fg) {
-    TrDwProb p{};
-    p.P = static_cast<int32_t>(P);
-    p.Q = static_cast<int32_t>(Q);
-    p.MB = static_cast<int32_t>(M / 32);
-    plan_splits(p, dA != nullptr);
-    const int64_t S = p.S;
-    // split-K partials are owned by the plan (their size follows its split plan)
-    p.part = empty(S * P * Q, torch::kFloat32).data_ptr<float>();
-    p.G = G;
-    p.X = X;
-    if (dA) {
-      TORCH_CHECK(P % 64 == 0, "TreePlan: routed dW needs P % 64 == 0");
-      p.route = 1;
-      p.dA = dA;
-      p.mask = mask;
-      p.logPg = logPg;
-      p.Fg = Fg;
-      p.include_self = self_;
-      p.inv = 1.f / static_cast<float>(Fg + self_);
-    }
-    probs_.push_back(p);
-  }
-
   void build_dw() {
-    // conv layers 0..L-1, then fc and out_fc
     for (int k = 0; k < L_; ++k) {
       const int64_t P = dims_[k], Q = 2 * Hin(k);
       const std::string ks = std::to_string(k);
       if (k < L_ - 1) {
         const int lvl = L_ - 1 - k;  // target level of layer k
-        add_prob("part" + ks, P, Q, M_[lvl], nullptr, bf("A" + ks + "_kt", M_[lvl] * Q),
-                 f32("dA" + std::to_string(k + 1), M_[lvl - 1] * 2 * P), i32_as_u32("mask" + ks, (M_[lvl] / 32) * P),
-                 static_cast<int>(logP_[lvl]), static_cast<int>(F_[lvl]));
+        dw_.add(P, Q, M_[lvl], nullptr, bf("A" + ks + "_kt", M_[lvl] * Q),
+                f32("dA" + std::to_string(k + 1), M_[lvl - 1] * 2 * P), i32_as_u32("mask" + ks, (M_[lvl] / 32) * P),
+                logP_[lvl], F_[lvl], self_);
       } else {
-        add_prob("part" + ks, P, Q, B_, bf("g_kt", B_ * P), bf("A" + ks + "_kt", B_ * Q), nullptr, nullptr, 0, 0);
+        dw_.add(P, Q, B_, bf("g_kt", B_ * P), bf("A" + ks + "_kt", B_ * Q), nullptr, nullptr, 0, 0, 0);
       }
     }
     const int64_t H = dims_[L_ - 1];
-    add_prob("part_fc", E_, H, B_, bf("demb_kt", (int64_t)B_ * E_), bf("h_kt", B_ * H), nullptr, nullptr, 0, 0);
-    add_prob("part_out", C_, E_, B_, bf("dlog_kt", (int64_t)B_ * C_), bf("emb_kt", (int64_t)B_ * E_), nullptr,
-             nullptr, 0, 0);
+    dw_.add(E_, H, B_, bf("demb_kt", (int64_t)B_ * E_), bf("h_kt", B_ * H), nullptr, nullptr, 0, 0, 0);
+    dw_.add(C_, E_, B_, bf("dlog_kt", (int64_t)B_ * C_), bf("emb_kt", (int64_t)B_ * E_), nullptr, nullptr, 0, 0, 0);
   }
 
   void build_opt() {
-    torch::Tensor flat = T("flat");
-    const int64_t n = flat.numel();
-    TrOptArgs& a = opt_;
-    a.p = f32("flat", n);
-    a.g = f32("grad", n);
-    a.m = f32("m", n);
-    a.v = f32("v", n);
-    a.n = n;
     std::vector<int64_t> off = getv("offsets");  // L convs, fc W, fc b, out W, end
-    TORCH_CHECK((int)off.size() == L_ + 4 && off.back() == n, "TreePlan: offsets must cover the flat buffer");
+    TORCH_CHECK((int)off.size() == L_ + 4 && off.back() == T("flat").numel(),
+                "TreePlan: offsets must cover the flat buffer");
     // segments: conv weights [H_k][2 Hin_k] (+ transposed shadows where a backward GEMM
-    // reads them), fc W [E][H], fc bias [E] (vector), out W [C][E]
-    const int64_t H = dims_[L_ - 1];
-    int seg = 0, blk = 0;
+    // reads them), fc W [E][H], fc bias [E] (vector: the head's per-block sums), out W [C][E]
+    const int64_t H = dims_[L_ - 1], nhead = B_ / kTrHeadRows;
     for (int k = 0; k < L_ + 3; ++k) {
-      TrSeg& s = a.seg[seg++];
-      s.off = off[k];
-      s.n = off[k + 1] - off[k];
-      s.blk0 = blk;
-      const bool bias = k == L_ + 1;
-      if (bias) {  // the head's per-block fc-bias sums
-        s.part = head_.dbfc_part;
-        s.S = static_cast<int32_t>(B_ / kTrHeadRows);
-        s.rows = 1;
-        s.cols = 0;
-        blk += tr_seg_prepare(s);
+      const int64_t n = off[k + 1] - off[k];
+      if (k == L_ + 1) {
+        dw_.add_vec_seg(off[k], n, head_.dbfc_part, nhead);
         continue;
       }
-      const int pi = k < L_ ? k : (k == L_ ? L_ : L_ + 1);
-      const TrDwProb& p = probs_[pi];
-      TORCH_CHECK(s.n == (int64_t)p.P * p.Q, "TreePlan: flat segment ", k, " does not match its dW problem");
-      s.part = p.part;
-      s.S = p.S;
-      s.rows = p.P;
-      s.cols = p.Q;
-      TORCH_CHECK(s.rows % 8 == 0 && s.cols % 32 == 0, "TreePlan: weight segments need rows % 8, cols % 32");
+      const TrDwProb& p = dw_.probs[k < L_ + 1 ? k : L_ + 1];
+      TORCH_CHECK(n == (int64_t)p.P * p.Q, "TreePlan: flat segment ", k, " does not match its dW problem");
       if (k < L_) {
         const std::string ks = std::to_string(k);
-        s.sh = bf("W" + ks + "_sh", s.n);
-        s.shT = k >= 1 ? bf("W" + ks + "_shT", s.n) : nullptr;
+        dw_.add_seg(off[k], p, bf("W" + ks + "_sh", n), k >= 1 ? bf("W" + ks + "_shT", n) : nullptr);
       } else if (k == L_) {
-        s.sh = bf("Wfc_sh", (int64_t)E_ * H);
-        s.shT = bf("Wfc_shT", (int64_t)E_ * H);
+        dw_.add_seg(off[k], p, bf("Wfc_sh", (int64_t)E_ * H), bf("Wfc_shT", (int64_t)E_ * H));
       } else {
-        s.sh = bf("Wout_sh", (int64_t)C_ * E_);
-        s.shT = bf("Wout_shT", (int64_t)C_ * E_);
+        dw_.add_seg(off[k], p, bf("Wout_sh", (int64_t)C_ * E_), bf("Wout_shT", (int64_t)C_ * E_));
       }
-      blk += tr_seg_prepare(s);
     }
-    a.nseg = seg;
-    a.nblk = blk;
-    a.smp = sample_;
-    a.nsample = static_cast<int32_t>((sample_.M + 63) / 64);
-    a.step = ptr<int64_t>("step", torch::kInt64, 1);
-    a.lr = static_cast<float>(getf("lr"));
-    a.b1 = static_cast<float>(getf("beta1"));
-    a.b2 = static_cast<float>(getf("beta2"));
-    a.eps = static_cast<float>(getf("eps"));
-    a.wd = static_cast<float>(getf("weight_decay"));
-    a.grad_scale = 1.f;
-    a.kind = static_cast<int32_t>(geti("opt_kind"));
-    a.head_part = head_.head_part;
-    a.nhead = static_cast<int32_t>(B_ / kTrHeadRows);
-    a.loss_acc = f32("loss_acc", 1);
-    a.counts = i32_as_u32("counts", 3);
-    a.loss_out = f32("loss_out", 1);
+    dw_.layout_segs();
+    dw_.fill_opt(off.back(), head_.head_part, nhead, false);
+    dw_.opt.smp = sample_;
+    dw_.opt.nsample = static_cast<int32_t>((sample_.M + 63) / 64);
   }
 };
 
@@ -777,7 +721,6 @@ class TowerPlan : private PlanDict {
     TORCH_CHECK(logP_ >= 4 && (1 << logP_) > F1_ && F1_ >= 1 && F2_ >= 1, "TowerPlan: slot group too small");
     TORCH_CHECK(D_ % 16 == 0 && H_ % 64 == 0, "TowerPlan: padded dims (D % 16, H % 64)");
     M_ = R_ << logP_;
-    route_impl_ = plan_route_impl(*this);
     // graph + tree; root_rows is used when the roots are drawn in the sampler (PairPlan), not
     // when they are given
     fill_graph_tree(*this, g_, tree_, F1_, 0, logP_, 0, static_cast<uint32_t>(geti("mask1")), 0u);
@@ -823,62 +766,30 @@ class TowerPlan : private PlanDict {
     bm_ = (1 << logP_) > 32 ? (1 << logP_) : 32;
     TORCH_CHECK(bm_ <= 128 && M_ % bm_ == 0, "TowerPlan: sibling groups of at most 128 rows");
     // routed dW of W0 (G routed from dA1 through the tree and the ReLU bits)
-    TrDwProb& p = prob_;
-    p.P = static_cast<int32_t>(H_);
-    p.Q = static_cast<int32_t>(2 * D_);
-    p.MB = static_cast<int32_t>(M_ / 32);
-    const int64_t tiles = (p.P / 64) * ((p.Q + 127) / 128);
-    const int64_t target = has("dw_route_wg") ? geti("dw_route_wg") : 256;
-    int64_t S = (target + tiles - 1) / tiles;
-    S = (S + 7) / 8 * 8;
-    if (S > (p.MB + 7) / 8 * 8) S = (p.MB + 7) / 8 * 8;
-    p.kps = static_cast<int32_t>((p.MB + S - 1) / S);
-    p.S = static_cast<int32_t>(S);
-    p.part = empty(S * p.P * p.Q, torch::kFloat32).data_ptr<float>();
-    p.G = nullptr;
-    p.X = a.a_kt;
-    p.route = 1;
-    p.dA = ptr<float>("dA1", torch::kFloat32, R_ * 2 * H_);
-    p.mask = a.mask;
-    p.logPg = static_cast<int32_t>(logP_);
-    p.Fg = static_cast<int32_t>(F1_);
-    p.include_self = static_cast<int32_t>(self_);
-    p.inv = 1.f / static_cast<float>(F1_ + self_);
+    const TrDwProb& p = dw_.add(H_, 2 * D_, M_, nullptr, a.a_kt, ptr<float>("dA1", torch::kFloat32, R_ * 2 * H_),
+                                a.mask, logP_, F1_, self_);
     // reduce into the fp32 gradient / bf16 shadow of the fp32 master (one weight segment)
-    TrOptArgs& o = opt_;
+    TrOptArgs& o = dw_.opt;
     float* w = ptr<float>("W0", torch::kFloat32, H_ * 2 * D_);
     o.p = o.m = o.v = w;
     o.g = ptr<float>("gW0", torch::kFloat32, H_ * 2 * D_);
     o.n = H_ * 2 * D_;
-    TrSeg& sg = o.seg[0];
-    sg.off = 0;
-    sg.n = o.n;
-    sg.part = p.part;
-    sg.S = p.S;
-    sg.rows = static_cast<int32_t>(H_);
-    sg.cols = static_cast<int32_t>(2 * D_);
-    sg.blk0 = 0;
-    sg.sh = const_cast<uint16_t*>(a.W);
-    sg.shT = nullptr;
-    o.nseg = 1;
-    o.nblk = tr_seg_prepare(sg);
+    dw_.add_seg(0, p, a.W, nullptr);
+    dw_.layout_segs();
     o.step = zeros_ptr<int64_t>(1, torch::kInt64);
     o.head_part = o.loss_acc = o.loss_out = zeros_ptr<float>(8, torch::kFloat32);
-    o.nhead = 0;
-    o.counts = nullptr;
-    o.nsample = 0;
     o.kind = 2;
-    plan_fuse_key(*this);  // accepted and checked; bwd() is a reduce into gW0 (mode 0), which keeps tr_opt
   }
 
   // the tower's backward hands a gradient to torch's optimizer: no optimizer in its dW launch
-  bool fused() const { return false; }
-  int64_t fuse_error() const { return 0; }
+  // (dw_opt_fuse is accepted and checked; bwd() is a reduce into gW0, mode 0, which keeps tr_opt)
+  bool fused() const { return dw_.fused(); }
+  int64_t fuse_error() const { return dw_.fuse_error(); }
 
   // refresh the bf16 fm shadow of W0 from the fp32 master (call after each update)
   void shadow() {
     const c10::DeviceGuard g(device());
-    tree_ok(eh_tr_opt(&opt_, 3, cur_stream()), "tower shadow");
+    tree_ok(eh_tr_opt(&dw_.opt, 3, cur_stream()), "tower shadow");
   }
   void sample() {
     const c10::DeviceGuard g(device());
@@ -892,7 +803,7 @@ class TowerPlan : private PlanDict {
   // routed dW description)
   const TrSampleArgs& sample_args() const { return sample_; }
   const TrFwdArgs& fwd_args() const { return fwd_; }
-  const TrDwProb& prob() const { return prob_; }
+  const TrDwProb& prob() const { return dw_.probs[0]; }
   int feat_fp32() const { return feat_fp32_; }
   int bm() const { return bm_; }
   int64_t R() const { return R_; }
@@ -902,24 +813,19 @@ class TowerPlan : private PlanDict {
 
   // dA1 (the plan's buffer) -> gW0 (the plan's buffer)
   void bwd() {
+    dw_.launch({0}, c10::nullopt, false, 1.0);
     const c10::DeviceGuard g(device());
-    TrDwLaunch L{};
-    L.route[0] = prob_;
-    L.nroute = 1;
-    L.route_impl = route_impl_;
-    tree_ok(eh_tr_dw(&L, cur_stream()), "tower dw");
-    tree_ok(eh_tr_opt(&opt_, 0, cur_stream()), "tower reduce");
+    tree_ok(eh_tr_opt(&dw_.opt, 0, cur_stream()), "tower reduce");
   }
 
  private:
   int64_t R_, F1_, F2_, logP_, D_, H_, self_, M_;
-  int feat_fp32_ = 0, bm_ = 32, route_impl_ = 2;
+  int feat_fp32_ = 0, bm_ = 32;
   TrGraph g_{};
   TrTree tree_{};
   TrSampleArgs sample_{};
   TrFwdArgs fwd_{};
-  TrDwProb prob_{};
-  TrOptArgs opt_{};
+  DwPlan dw_{*this};  // the routed W0 problem and its segment
 
   int32_t* owned_i32(int64_t n) { return full(n, -1, torch::kInt32).data_ptr<int32_t>(); }
 };
@@ -962,13 +868,11 @@ class PairPlan : private PlanDict {
     sc_.tr.pair_mask = static_cast<uint32_t>(geti("pos_mask"));
     sc_.tr.stream_off = 8;
     // forwards: the source tower's block 0 advances the Adam step and the RNG counter
-    step_ = T("step");
-    need(step_, torch::kInt64, 1, "step");
     fs_ = s.fwd_args();
     fc_ = c.fwd_args();
     fs_.roots_in = ss_.roots;  // roots_cur: the roots the samplers drew
     fc_.roots_in = sc_.roots;
-    fs_.step = step_.data_ptr<int64_t>();
+    fs_.step = ptr<int64_t>("step", torch::kInt64, 1);
     fc_.step = nullptr;
     fc_.rng = zeros_ptr<int64_t>(2, torch::kInt64);
     // head
@@ -983,75 +887,33 @@ class PairPlan : private PlanDict {
     h.head_part = zeros_ptr<float>(nblk_ * 4, torch::kFloat32);
     tower(h.s, s, "s");
     tower(h.c, c, "c");
-    // dW: routed W0 of both towers + W1 / Wfc of both towers
-    L_.route[0] = s.prob();
-    L_.route[1] = c.prob();
-    L_.nroute = 2;
-    L_.route_impl = plan_route_impl(*this);
-    L_.plain.n = 0;
-    const char* tn[2] = {"s", "c"};
-    const int64_t R[2] = {B_, B_ * (1 + K_)};
-    const TrPairTower* tw[2] = {&h.s, &h.c};
-    for (int t = 0; t < 2; ++t) {
-      plain_[2 * t] = add_plain(H1_, 2 * H0_, R[t], tw[t]->g_kt, tw[t]->A1_kt);   // dW1 = g^T A1
-      plain_[2 * t + 1] = add_plain(E_, H1_, R[t], tw[t]->de_kt, tw[t]->h_kt);   // dWfc = de^T h1
-    }
-    (void)tn;
-    // optimizer over the flat buffer: per tower W0, W1, Wfc, bfc
-    TrOptArgs& o = opt_;
-    torch::Tensor flat = T("flat");
-    need(flat, torch::kFloat32, -1, "flat");
-    std::vector<int64_t> off = getv("offsets");
-    // the flat buffers may end in padding (parallel/flat.py pads to a multiple of 8)
-    TORCH_CHECK(off.size() == 9 && off.back() <= flat.numel(), "PairPlan: offsets = 8 segments + end");
-    o.n = off.back();
-    const int64_t nbuf = flat.numel();
-    o.p = flat.data_ptr<float>();
-    o.g = ptr<float>("grad", torch::kFloat32, nbuf);
-    o.m = ptr<float>("m", torch::kFloat32, nbuf);
-    o.v = ptr<float>("v", torch::kFloat32, nbuf);
-    int blk = 0, seg = 0;
+    // dW: routed W0 of both towers (their plans and partials), then W1 / Wfc of each tower
     const TowerPlan* tp[2] = {&s, &c};
+    const TrPairTower* tw[2] = {&h.s, &h.c};
+    for (int t = 0; t < 2; ++t) dw_.probs.push_back(tp[t]->prob());
+    for (int t = 0; t < 2; ++t) {
+      dw_.add(H1_, 2 * H0_, tp[t]->R(), tw[t]->g_kt, tw[t]->A1_kt, nullptr, nullptr, 0, 0, 0);  // dW1 = g^T A1
+      dw_.add(E_, H1_, tp[t]->R(), tw[t]->de_kt, tw[t]->h_kt, nullptr, nullptr, 0, 0, 0);      // dWfc = de^T h1
+    }
+    // optimizer over the flat buffer, which may end in padding (parallel/flat.py pads to a
+    // multiple of 8): per tower W0, W1, Wfc, bfc
+    std::vector<int64_t> off = getv("offsets");
+    TORCH_CHECK(off.size() == 9, "PairPlan: offsets = 8 segments + end");
     for (int t = 0; t < 2; ++t) {
       const TrPairTower& T_ = *tw[t];
-      const TrDwProb& W0 = tp[t]->prob();
-      add_seg(seg++, blk, off[4 * t], W0.part, W0.S, W0.P, W0.Q, const_cast<uint16_t*>(tp[t]->fwd_args().W), nullptr);
-      const TrDwProb& W1 = L_.plain.p[plain_[2 * t]];
-      add_seg(seg++, blk, off[4 * t + 1], W1.part, W1.S, W1.P, W1.Q, const_cast<uint16_t*>(T_.W1),
-              const_cast<uint16_t*>(T_.W1T));
-      const TrDwProb& Wf = L_.plain.p[plain_[2 * t + 1]];
-      add_seg(seg++, blk, off[4 * t + 2], Wf.part, Wf.S, Wf.P, Wf.Q, const_cast<uint16_t*>(T_.Wfc),
-              const_cast<uint16_t*>(T_.WfcT));
-      add_seg(seg++, blk, off[4 * t + 3], T_.dbfc_part, static_cast<int32_t>(nblk_), 1, 0, nullptr, nullptr);
+      dw_.add_seg(off[4 * t], dw_.probs[t], tp[t]->fwd_args().W, nullptr);
+      dw_.add_seg(off[4 * t + 1], dw_.probs[2 + 2 * t], T_.W1, T_.W1T);
+      dw_.add_seg(off[4 * t + 2], dw_.probs[3 + 2 * t], T_.Wfc, T_.WfcT);
+      dw_.add_vec_seg(off[4 * t + 3], E_, T_.dbfc_part, nblk_);
       TORCH_CHECK(off[4 * t + 4] - off[4 * t + 3] == E_, "PairPlan: bias segment must be E long");
     }
-    o.nseg = seg;
-    o.nblk = blk;
-    o.step = step_.data_ptr<int64_t>();
-    o.lr = static_cast<float>(getf("lr"));
-    o.b1 = static_cast<float>(getf("beta1"));
-    o.b2 = static_cast<float>(getf("beta2"));
-    o.eps = static_cast<float>(getf("eps"));
-    o.wd = static_cast<float>(getf("weight_decay"));
-    o.grad_scale = 1.f;
-    o.kind = static_cast<int32_t>(geti("opt_kind"));
-    o.head_part = h.head_part;
-    o.nhead = static_cast<int32_t>(nblk_);
-    o.loss_acc = ptr<float>("loss_acc", torch::kFloat32, 1);
-    o.loss_out = ptr<float>("loss_out", torch::kFloat32, 1);
-    o.stat_f = ptr<float>("mrr_sum", torch::kFloat32, 1);
-    o.counts = nullptr;
-    o.nsample = 0;
-    TrDwOpt f;
-    int64_t lines = 0;
-    if (plan_fuse_key(*this) && fill_dw_opt(L_, opt_, f, lines)) {
-      fused_ = true;
-      sync_ = zeros(lines * kTrSyncLine, torch::kInt32);
-    }
+    dw_.layout_segs();
+    dw_.fill_opt(off.back(), h.head_part, nblk_, true);
+    dw_.try_fuse(true);
   }
 
-  bool fused() const { return fused_; }
-  int64_t fuse_error() const { return fuse_status(sync_); }
+  bool fused() const { return dw_.fused(); }
+  int64_t fuse_error() const { return dw_.fuse_error(); }
 
   void sample() {
     const c10::DeviceGuard g(device());
@@ -1068,47 +930,19 @@ class PairPlan : private PlanDict {
     tree_ok(eh_tr_pair_head(&head_, cur_stream()), "pair head");
   }
   // fuse (a fused() plan): the launch also runs the optimizer, what opt(2, grad_scale) would do
-  void dw(bool fuse, double grad_scale) {
-    const c10::DeviceGuard g(device());
-    TrDwLaunch L = L_;
-    if (fuse) {
-      TORCH_CHECK(fused_, "pair dw: the plan is not fused()");
-      TrOptArgs o = opt_;
-      o.grad_scale = static_cast<float>(grad_scale);
-      int64_t lines = 0;
-      TORCH_CHECK(fill_dw_opt(L, o, L.opt, lines) && lines * kTrSyncLine == sync_.numel(), "pair dw: fused plan changed");
-      L.opt.sync = reinterpret_cast<uint32_t*>(sync_.data_ptr<int32_t>());
-      L.fuse = 1;
-    }
-    tree_ok(eh_tr_dw(&L, cur_stream()), fuse ? "pair dw+opt" : "pair dw");
-  }
+  void dw(bool fuse, double grad_scale) { dw_.launch(dw_.all(), c10::nullopt, fuse, grad_scale); }
   // 0: split-K reduce into the flat gradient; 1: optimizer from it (scaled); 2: both; 3: shadows
   void opt(int mode, double grad_scale) {
     const c10::DeviceGuard g(device());
-    TrOptArgs a = opt_;
+    TrOptArgs a = dw_.opt;
     a.grad_scale = static_cast<float>(grad_scale);
     tree_ok(eh_tr_opt(&a, mode, cur_stream()), "pair opt");
   }
-  void set_lr(double lr) { opt_.lr = static_cast<float>(lr); }
-  void set_grad(torch::Tensor g) {
-    need(g, torch::kFloat32, -1, "grad");
-    TORCH_CHECK(g.numel() >= opt_.n, "grad has ", g.numel(), " elements, fewer than the ", opt_.n, " parameters");
-    grad_keep_ = g;
-    opt_.g = g.data_ptr<float>();
-  }
+  void set_lr(double lr) { dw_.set_lr(lr); }
+  void set_grad(torch::Tensor g) { dw_.set_grad(g, false); }
   // the dW launch's problems, routed first: slabs the optimizer sums / slabs summed in the block
-  std::vector<int64_t> splits() const {
-    std::vector<int64_t> s;
-    for (int r = 0; r < L_.nroute; ++r) s.push_back(L_.route[r].S);
-    for (int i = 0; i < L_.plain.n; ++i) s.push_back(L_.plain.p[i].S);
-    return s;
-  }
-  std::vector<int64_t> folds() const {
-    std::vector<int64_t> f;
-    for (int r = 0; r < L_.nroute; ++r) f.push_back(L_.route[r].F);
-    for (int i = 0; i < L_.plain.n; ++i) f.push_back(L_.plain.p[i].F);
-    return f;
-  }
+  std::vector<int64_t> splits() const { return dw_.splits(); }
+  std::vector<int64_t> folds() const { return dw_.folds(); }
 
  private:
   int64_t B_, K_, H0_, H1_, E_, nblk_;
@@ -1116,11 +950,7 @@ class PairPlan : private PlanDict {
   TrSampleArgs ss_{}, sc_{};
   TrFwdArgs fs_{}, fc_{};
   TrPairHeadArgs head_{};
-  TrDwLaunch L_{};
-  int plain_[4] = {0, 0, 0, 0};
-  TrOptArgs opt_{};
-  torch::Tensor step_, grad_keep_, sync_;
-  bool fused_ = false;
+  DwPlan dw_{*this};  // W0 of both towers (routed), then W1, Wfc of the source and of the context tower
 
   void tower(TrPairTower& t, const TowerPlan& tp, const std::string& x) {
     const int64_t R = tp.R();
@@ -1136,40 +966,6 @@ class PairPlan : private PlanDict {
     t.g_kt = zeros_ptr<uint16_t>(R * H1_, torch::kBFloat16);
     t.dA1 = const_cast<float*>(tp.prob().dA);
     t.dbfc_part = zeros_ptr<float>(nblk_ * E_, torch::kFloat32);
-  }
-
-  // stored-G dW problem (plan_stored: the split plan TreePlan uses)
-  int add_plain(int64_t P, int64_t Q, int64_t M, const uint16_t* G, const uint16_t* X) {
-    TORCH_CHECK(M % 32 == 0 && P % 32 == 0 && Q % 32 == 0, "PairPlan: dW problem shapes");
-    TrDwProb p{};
-    p.P = static_cast<int32_t>(P);
-    p.Q = static_cast<int32_t>(Q);
-    p.MB = static_cast<int32_t>(M / 32);
-    plan_stored(*this, p);
-    p.part = zeros_ptr<float>(static_cast<int64_t>(p.S) * P * Q, torch::kFloat32);
-    p.G = G;
-    p.X = X;
-    TORCH_CHECK(L_.plain.n < kTrMaxProbs, "PairPlan: too many dW problems");
-    L_.plain.p[L_.plain.n] = p;
-    return L_.plain.n++;
-  }
-
-  void add_seg(int seg, int& blk, int64_t off, const float* part, int32_t S, int64_t rows, int64_t cols, uint16_t* sh,
-               uint16_t* shT) {
-    TORCH_CHECK(seg < kTrMaxSegs, "PairPlan: too many optimizer segments");
-    TrSeg& g = opt_.seg[seg];
-    g.off = off;
-    g.n = cols > 0 ? rows * cols : E_;
-    g.part = part;
-    g.S = S;
-    g.rows = static_cast<int32_t>(rows);
-    g.cols = static_cast<int32_t>(cols);
-    g.blk0 = blk;
-    g.sh = sh;
-    g.shT = shT;
-    if (cols > 0)
-      TORCH_CHECK(rows % 8 == 0 && cols % 32 == 0, "PairPlan: weight segments need rows % 8, cols % 32");
-    blk += tr_seg_prepare(g);
   }
 };
 

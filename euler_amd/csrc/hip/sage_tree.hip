@@ -23,7 +23,7 @@
 #include <cstdlib>
 
 #include "hip/tile.h"
-#include "hip/tree_args.h"
+#include "hip/tree_plan.h"
 
 namespace euler_hip {
 
@@ -2214,7 +2214,7 @@ __device__ __forceinline__ void tr_opt_tile(const A& a, int b, float (*tile_s)[3
   int64_t i;
   int r = 0, c = 0;
   bool valid = true;
-  // vector segment with slab groups (tr_seg_prepare): thread = (group, element); uniform per block
+  // vector segment with slab groups (tr_seg_layout): thread = (group, element); uniform per block
   const int grp = sg.cols == 0 && sg.sgrp > 1 ? sg.sgrp : 1;
   const int per = 256 / grp, sub = tid / per;
   if (sg.cols > 0) {  // 8 x 32 tile of a weight matrix
@@ -2575,76 +2575,13 @@ hipError_t eh_tr_pair_head(const TrPairHeadArgs* a, hipStream_t s) {
   return hipGetLastError();
 }
 
+static_assert(kRP == kTrRouteP && kRQ == kTrRouteQ, "tree_plan.h plans the routed tiles of tr_dw_route");
+
 hipError_t eh_tr_dw(TrDwLaunch* L, hipStream_t s) {
-  TrDwProbs* pr = &L->plain;
-  if (pr->n < 0 || pr->n > kTrMaxProbs || L->nroute < 0 || L->nroute > 2) return hipErrorInvalidValue;
-  L->rwg[0] = 0;
-  for (int r = 0; r < L->nroute; ++r) {
-    TrDwProb* p = &L->route[r];
-    if (!p->route || !p->dA || !p->mask || !p->X || !p->part) return hipErrorInvalidValue;
-    if (p->P % kRP != 0 || p->Q % 32 != 0 || p->MB < 1 || p->kps < 1 || p->logPg < 3) return hipErrorInvalidValue;
-    // the XCD-aware block mapping needs S % 8 == 0 (splits past MB write zero slabs)
-    if (p->S % 8 != 0 || static_cast<int64_t>(p->S) * p->kps < p->MB) return hipErrorInvalidValue;
-    p->tiles_q = static_cast<int>(ceil_div(p->Q, kRQ));
-    p->ntiles = (p->P / kRP) * p->tiles_q;
-    p->wg0 = 0;
-    L->rwg[r + 1] = L->rwg[r] + p->ntiles * p->S;
-  }
-  int wg = 0;
-  for (int i = 0; i < pr->n; ++i) {
-    TrDwProb& p = pr->p[i];
-    if (p.P % 32 != 0 || p.Q % 32 != 0 || p.MB < 1 || p.kps < 1) return hipErrorInvalidValue;
-    if (p.route || !p.G || !p.X || !p.part) return hipErrorInvalidValue;
-    if (p.F < 0 || p.F > kTrFoldMax || p.S < 1) return hipErrorInvalidValue;
-    if (p.F > 0) {  // folded: F slabs cover K, one `part` slab, one workgroup per 32x32 tile
-      if (p.S != 1 || static_cast<int64_t>(p.F) * p.kps < p.MB) return hipErrorInvalidValue;
-      p.tiles_q = p.Q / 32;
-      p.ntiles = (p.P / 32) * p.tiles_q;
-      p.wg0 = wg;
-      wg += p.ntiles;
-      continue;
-    }
-    if (static_cast<int64_t>(p.S) * p.kps < p.MB) return hipErrorInvalidValue;
-    p.tiles_q = (p.Q + 63) / 64;
-    p.ntiles = ((p.P + 63) / 64) * p.tiles_q;
-    p.wg0 = wg;
-    wg += p.ntiles * p.S;
-  }
-  int total = L->rwg[L->nroute] + wg;
-  if (total == 0) return hipSuccess;
-  L->ndw = total;
-  if (L->fuse) {
-    // the optimizer in the launch: every stored-G problem folded with a flat segment of its own,
-    // the trailing segments vectors first, then one weight segment per routed problem whose slabs
-    // are that problem's, and a hand-off line for the ticket, the status and every routed tile
-    TrDwOpt& o = L->opt;
-    if (L->fuse != 1 || !o.p || !o.m || !o.v || !o.step || !o.loss_acc || !o.loss_out || !o.head_part || o.nhead < 1 ||
-        !o.sync || o.timeout < 1 || o.nseg < 1 || o.nseg > kTrMaxSegs || o.rseg0 < 0 ||
-        o.rseg0 + L->nroute != o.nseg)
-      return hipErrorInvalidValue;
-    for (int i = 0; i < pr->n; ++i)
-      if (pr->p[i].F < 1 || o.fseg[i].off < 0 || o.fseg[i].off % 4 != 0 || (o.fseg[i].shT && !o.fseg[i].sh))
-        return hipErrorInvalidValue;
-    int blk = 0, line = 2;
-    for (int k = 0; k < o.nseg; ++k) {
-      const TrSeg& g = o.seg[k];
-      if (!g.part || g.S < 1 || g.blk0 != blk) return hipErrorInvalidValue;
-      if (k < o.rseg0) {
-        if (g.cols != 0 || g.sh || g.shT || g.sgrp != tr_seg_groups(g)) return hipErrorInvalidValue;
-      } else {
-        const TrDwProb& p = L->route[k - o.rseg0];
-        if (g.part != p.part || g.S != p.S || g.rows != p.P || g.cols != p.Q ||
-            static_cast<int64_t>(g.rows) * g.cols != g.n || (g.shT && !g.sh))
-          return hipErrorInvalidValue;
-        o.cnt0[k - o.rseg0] = line;
-        line += p.ntiles;
-      }
-      blk += tr_seg_blocks(g);
-    }
-    if (blk != o.nblk || line != o.nsync) return hipErrorInvalidValue;
-    total += blk;
-  }
-  hipLaunchKernelGGL(tr_dw_all_kernel, dim3(static_cast<uint32_t>(total)), dim3(256), 0, s, *L);
+  TrDwGrid grid;
+  if (!tr_dw_layout(*L, grid)) return hipErrorInvalidValue;
+  if (grid.ndw == 0) return hipSuccess;
+  hipLaunchKernelGGL(tr_dw_all_kernel, dim3(static_cast<uint32_t>(grid.ndw + grid.ntrail)), dim3(256), 0, s, *L);
   return hipGetLastError();
 }
 
@@ -2657,23 +2594,10 @@ hipError_t eh_tr_opt(const TrOptArgs* ain, int mode, hipStream_t s) {
   const TrOptArgs* a = &A;
   if (!(mode == 1 || mode == 2)) A.nsample = 0;  // the sampler runs in modes 1/2 only
   if (mode == 3) A.ngather = 0;
-  if (a->nseg < 1 || a->nseg > kTrMaxSegs || a->nblk < 1) return hipErrorInvalidValue;
   if (!a->p || !a->g || !a->m || !a->v || !a->step || !a->loss_acc || !a->loss_out || !a->head_part ||
       a->nhead < 0 || (a->nhead == 0 && mode != 0 && mode != 3))
     return hipErrorInvalidValue;
-  int blk = 0;
-  for (int i = 0; i < a->nseg; ++i) {
-    const TrSeg& g = a->seg[i];
-    if (!g.part || g.S < 1 || g.blk0 != blk) return hipErrorInvalidValue;
-    if (g.cols > 0) {
-      if (g.rows % 8 != 0 || g.cols % 32 != 0 || static_cast<int64_t>(g.rows) * g.cols != g.n)
-        return hipErrorInvalidValue;
-    } else {
-      if (g.sh || g.shT || g.sgrp != tr_seg_groups(g)) return hipErrorInvalidValue;  // tr_seg_prepare
-    }
-    blk += tr_seg_blocks(g);
-  }
-  if (blk != a->nblk) return hipErrorInvalidValue;
+  if (a->nblk < 1 || tr_seg_layout(A.seg, a->nseg, false) != a->nblk) return hipErrorInvalidValue;
   int extra = 0;
   if (a->nsample > 0) {
     const TrSampleArgs& m = a->smp;

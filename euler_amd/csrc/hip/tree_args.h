@@ -188,22 +188,7 @@ struct TrDwProbs {
 };
 // the in-block fold keeps one 32x32 fp32 tile (4 KiB) per slab in the dW launch's LDS
 constexpr int kTrFoldLds = 64 * 1024;  // == sizeof(RouteLds), the area the fold aliases
-constexpr int kTrFoldMax = kTrFoldLds / (32 * 32 * 4);
-// split-K plan of a stored-G problem (P, Q, MB set): ~target workgroups of 64x64 tiles, at
-// least min_kps 32-row k-blocks per slab.  With `fold` and at most kTrFoldMax slabs the block
-// sums them (F = the slab count, S = 1: `part` and the optimizer see one slab); more slabs
-// keep the global path (F = 0, S = the slab count).
-inline void tr_plan_stored(TrDwProb& p, int64_t target, int64_t min_kps, bool fold) {
-  const int64_t MB = p.MB;
-  const int64_t tiles = ((p.P + 63) / 64) * ((p.Q + 63) / 64);
-  int64_t kps = (MB * tiles + target - 1) / target;
-  if (kps < min_kps) kps = min_kps;
-  if (kps > MB) kps = MB;
-  const int64_t slabs = (MB + kps - 1) / kps;
-  p.kps = static_cast<int32_t>(kps);
-  p.F = fold && slabs <= kTrFoldMax ? static_cast<int32_t>(slabs) : 0;
-  p.S = p.F ? 1 : static_cast<int32_t>(slabs);
-}
+constexpr int kTrFoldMax = kTrFoldLds / (32 * 32 * 4);  // split plans: tree_plan.h
 
 // flat parameter buffer segments: gradient = sum of S partials [S][n] (split-K slabs of a
 // dW problem, or the head's per-block fc-bias sums).  Weight matrices (cols > 0, rows % 8
@@ -218,22 +203,8 @@ struct TrSeg {
   int32_t blk0;        // first block of the segment
   uint16_t* sh;        // optional fm [rows][cols]
   uint16_t* shT;       // optional fm [cols][rows]
-  int32_t sgrp;        // vector segments: slab groups per element (1 or 4; tr_seg_prepare)
+  int32_t sgrp;        // vector segments: slab groups per element (1 or 4; tr_seg_layout, tree_plan.h)
 };
-// vector segments with many split-K slabs (the fc bias: one slab per head block) spread each
-// element's slab sum over 4 threads (256 / 4 elements per block): one round of 16 loads in
-// flight per thread instead of S / 16 dependent rounds, which made the bias block the tail
-// of the optimizer launch.  Returns the segment's block count.
-inline int tr_seg_groups(const TrSeg& s) { return s.cols == 0 && s.S > 16 ? 4 : 1; }
-inline int tr_seg_blocks(const TrSeg& s) {
-  if (s.cols > 0) return (s.rows / 8) * (s.cols / 32);
-  const int64_t per = 256 / tr_seg_groups(s);
-  return static_cast<int>((s.n + per - 1) / per);
-}
-inline int tr_seg_prepare(TrSeg& s) {
-  s.sgrp = tr_seg_groups(s);
-  return tr_seg_blocks(s);
-}
 struct TrOptArgs {
   float *p, *g, *m, *v;
   uint16_t* g16;  // optional bf16 gradient (data parallel: the all-reduce moves half the bytes);

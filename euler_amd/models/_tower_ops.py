@@ -27,6 +27,15 @@ import torch.nn.functional as F
 _HEAD_GEMM = os.environ.get("EULER_AMD_TOWER_GEMM", "gemm")
 
 
+def env_plan_keys(d, *names):
+    """Tuning environment -> keys of a tree plan's dict (csrc/hip/binding_tree.cpp): for every
+    name a plan reads, a set and non-empty ``EULER_AMD_<NAME>`` becomes ``d["<name>"]`` as an int."""
+    for name in names:
+        val = os.environ.get("EULER_AMD_" + name)
+        if val:
+            d[name.lower()] = int(val)
+
+
 def _mm(a, b, out=None, trans_a=False, trans_b=False, relu=False, bias=None, rmask=None, wgrad=False):
     from euler_amd.ops.gnn_ops import _gemm_splits, gemm
 

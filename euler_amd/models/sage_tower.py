@@ -36,7 +36,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from euler_amd.models._tower_ops import pair_loss, tower_head
+from euler_amd.models._tower_ops import env_plan_keys, pair_loss, tower_head
 from euler_amd.ops import mp_ops
 from euler_amd.ops._native import hip
 from euler_amd.parallel.flat import FlatOptimizer, FlatParams
@@ -110,10 +110,9 @@ class _Tower:
                  "A0_kt": torch.empty(self.M * 2 * self.D, dtype=torch.bfloat16, device=device),
                  "mask0": torch.zeros((self.M // 32) * self.H0, **i32), "A1": self.A1, "dA1": self.dA1,
                  "gW0": self.gW0}
-            if os.environ.get("EULER_AMD_DW_ROUTE_IMPL"):  # body of the routed W0 problem (0: the baseline)
-                d["dw_route_impl"] = int(os.environ["EULER_AMD_DW_ROUTE_IMPL"])
-            if os.environ.get("EULER_AMD_DW_OPT_FUSE"):  # checked; the tower's backward keeps its reduce launch
-                d["dw_opt_fuse"] = int(os.environ["EULER_AMD_DW_OPT_FUSE"])
+            # body of the routed W0 problem (0: the baseline); the fuse key is checked only: the
+            # tower's backward keeps its reduce launch
+            env_plan_keys(d, "DW_ROUTE_IMPL", "DW_OPT_FUSE")
             self._keep = d
             self.plan = hip().TowerPlan(d)
 
@@ -215,12 +214,9 @@ class UnsupSageTrainer:
             d[f"Wfc_sh_{x}"] = torch.zeros(E * H1, **bf)
             d[f"Wfc_shT_{x}"] = torch.zeros(E * H1, **bf)
             d[f"bfc_{x}"] = self.params[f"{t}.bfc"]
-        if os.environ.get("EULER_AMD_DW_FOLD"):  # 0: the W1 / Wfc split-K slabs go through memory
-            d["dw_fold"] = int(os.environ["EULER_AMD_DW_FOLD"])
-        if os.environ.get("EULER_AMD_DW_ROUTE_IMPL"):
-            d["dw_route_impl"] = int(os.environ["EULER_AMD_DW_ROUTE_IMPL"])
-        if os.environ.get("EULER_AMD_DW_OPT_FUSE"):  # 0: the optimizer keeps a launch of its own
-            d["dw_opt_fuse"] = int(os.environ["EULER_AMD_DW_OPT_FUSE"])
+        # DW_FOLD 0: the W1 / Wfc split-K slabs go through memory; DW_OPT_FUSE 0: the optimizer
+        # keeps a launch of its own
+        env_plan_keys(d, "DW_FOLD", "DW_ROUTE_IMPL", "DW_OPT_FUSE")
         self._pair_keep = d
         self.pair = hip().PairPlan(self.towers["gnn"].plan, self.towers["context_gnn"].plan, d)
         self.pair.opt(3)  # bf16 shadows of every weight

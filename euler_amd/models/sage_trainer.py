@@ -44,6 +44,7 @@ import torch.nn.functional as F
 
 from euler_amd.ops import mp_ops
 from euler_amd.ops._native import hip
+from euler_amd.models._tower_ops import env_plan_keys
 from euler_amd.models.captured import new_graph
 
 __all__ = ["SageTrainer", "sage_param_names"]
@@ -323,10 +324,8 @@ class SageTrainer:
              "offsets": self.offsets, "loss_acc": self.loss_acc, "loss_out": self.loss_out, "counts": self.counts,
              "lr": self.lr, "beta1": self.betas[0], "beta2": self.betas[1], "eps": self.eps,
              "weight_decay": self.wd, "opt_kind": _OPT_KIND[self.opt_name]}
-        for key in ("EULER_AMD_DW_TARGET_WG", "EULER_AMD_DW_MIN_KPS", "EULER_AMD_DW_ROUTE_WG", "EULER_AMD_FWD_BM",
-                    "EULER_AMD_DW_ROUTE_IMPL", "EULER_AMD_DW_FOLD", "EULER_AMD_DW_OPT_FUSE"):
-            if os.environ.get(key):
-                d[key[len("EULER_AMD_"):].lower()] = int(os.environ[key])
+        env_plan_keys(d, "DW_TARGET_WG", "DW_MIN_KPS", "DW_ROUTE_WG", "FWD_BM", "DW_ROUTE_IMPL", "DW_FOLD",
+                      "DW_OPT_FUSE")
         M_last = self.M[L - 1]
         FL = self.fanouts[-1]
         self.roots = torch.zeros(B, **i32)
