@@ -1,4 +1,4 @@
-// torch binding of the fused GraphSAGE tree step (sage_tree.hip).
+// torch binding of the fused GraphSAGE tree step (tree_fwd.hip, tree_head.hip, tree_dw.hip).
 //
 // A TreePlan is built once per trainer from a dict of device tensors and sizes: every
 // operand is validated here (PlanDict, binding_util.h: dtype, device, contiguity and the exact
@@ -174,20 +174,21 @@ class DwPlan {
     opt.g = pd_.f32("grad", nbuf);
     opt.m = pd_.f32("m", nbuf);
     opt.v = pd_.f32("v", nbuf);
-    opt.step = pd_.ptr<int64_t>("step", torch::kInt64, 1);
-    opt.lr = static_cast<float>(pd_.getf("lr"));
-    opt.b1 = static_cast<float>(pd_.getf("beta1"));
-    opt.b2 = static_cast<float>(pd_.getf("beta2"));
-    opt.eps = static_cast<float>(pd_.getf("eps"));
-    opt.wd = static_cast<float>(pd_.getf("weight_decay"));
-    opt.grad_scale = 1.f;
-    opt.kind = static_cast<int32_t>(pd_.geti("opt_kind"));
-    opt.head_part = head_part;
-    opt.nhead = static_cast<int32_t>(nhead);
-    opt.loss_acc = pd_.f32("loss_acc", 1);
-    opt.loss_out = pd_.f32("loss_out", 1);
-    if (rank_stat) opt.stat_f = pd_.f32("mrr_sum", 1);
-    else opt.counts = reinterpret_cast<uint32_t*>(pd_.i32("counts", 3));
+    TrOptCore& c = opt.c;
+    c.step = pd_.ptr<int64_t>("step", torch::kInt64, 1);
+    c.lr = static_cast<float>(pd_.getf("lr"));
+    c.b1 = static_cast<float>(pd_.getf("beta1"));
+    c.b2 = static_cast<float>(pd_.getf("beta2"));
+    c.eps = static_cast<float>(pd_.getf("eps"));
+    c.wd = static_cast<float>(pd_.getf("weight_decay"));
+    c.grad_scale = 1.f;
+    c.kind = static_cast<int32_t>(pd_.geti("opt_kind"));
+    c.head_part = head_part;
+    c.nhead = static_cast<int32_t>(nhead);
+    c.loss_acc = pd_.f32("loss_acc", 1);
+    c.loss_out = pd_.f32("loss_out", 1);
+    if (rank_stat) c.stat_f = pd_.f32("mrr_sum", 1);
+    else c.counts = reinterpret_cast<uint32_t*>(pd_.i32("counts", 3));
   }
 
   // plan key dw_opt_fuse: the launch of every problem carries the optimizer, where the plan
@@ -218,7 +219,7 @@ class DwPlan {
     const c10::DeviceGuard g(pd_.device());
     TrDwGrid grid;
     TrDwLaunch L = launch_of(which, fuse, grid);
-    if (fuse) L.opt.grad_scale = static_cast<float>(grad_scale);
+    if (fuse) L.opt.c.grad_scale = static_cast<float>(grad_scale);
     if (prof.has_value()) {
       pd_.need(*prof, torch::kInt64, -1, "prof");
       L.prof = reinterpret_cast<long long*>(prof->data_ptr<int64_t>());
@@ -242,7 +243,7 @@ class DwPlan {
     for (const auto& p : probs) f.push_back(p.F);
     return f;
   }
-  void set_lr(double lr) { opt.lr = static_cast<float>(lr); }
+  void set_lr(double lr) { opt.c.lr = fopt_.c.lr = static_cast<float>(lr); }
   // the flat fp32 gradient the reduce writes and the optimizer reads (e.g. a view of the xGMI
   // all-reduce's IPC input region, so the all-reduce runs in place there); exact: of opt.n
   // elements, else at least as many
@@ -257,7 +258,7 @@ class DwPlan {
   PlanDict& pd_;
   int route_impl_;
   bool fuse_key_, fused_ = false;
-  TrDwOpt fopt_{};      // the optimizer of the fused launch of all(); lr follows opt.lr
+  TrDwOpt fopt_{};      // the optimizer of the fused launch of all(); set_lr keeps its lr equal to opt's
   torch::Tensor sync_;  // its hand-off state (TrDwOpt::sync)
   torch::Tensor grad_;
 
@@ -287,7 +288,6 @@ class DwPlan {
       TORCH_CHECK(fused_ && every, pd_.name(),
                   ": the optimizer runs in the dW launch of every problem, in the plan's order, of a fused() plan only");
       L.opt = fopt_;
-      L.opt.lr = opt.lr;
       L.fuse = 1;
     }
     TORCH_CHECK(tr_dw_layout(L, grid), pd_.name(), ": the dW launch is not one the kernel takes");
@@ -399,7 +399,7 @@ class TreePlan : private PlanDict {
     const c10::DeviceGuard g(device());
     TORCH_CHECK(!with_gather || pipeline_ok(), "TreePlan: no pipelined gather for this plan");
     TrOptArgs a = dw_.opt;
-    a.grad_scale = static_cast<float>(grad_scale);
+    a.c.grad_scale = static_cast<float>(grad_scale);
     if (!with_sample) a.nsample = 0;
     if (with_gather) {
       a.gat = fwd0_;
@@ -441,7 +441,7 @@ class TreePlan : private PlanDict {
     }
     a.nblk = tr_seg_layout(a.seg, a.nseg, true);
     a.nsample = 0;
-    if (!head_stats) a.nhead = 0;
+    if (!head_stats) a.c.nhead = 0;
     tree_ok(eh_tr_opt(&a, 0, cur_stream()), "tr_opt(segments)");
   }
 
@@ -776,9 +776,9 @@ class TowerPlan : private PlanDict {
     o.n = H_ * 2 * D_;
     dw_.add_seg(0, p, a.W, nullptr);
     dw_.layout_segs();
-    o.step = zeros_ptr<int64_t>(1, torch::kInt64);
-    o.head_part = o.loss_acc = o.loss_out = zeros_ptr<float>(8, torch::kFloat32);
-    o.kind = 2;
+    o.c.step = zeros_ptr<int64_t>(1, torch::kInt64);
+    o.c.head_part = o.c.loss_acc = o.c.loss_out = zeros_ptr<float>(8, torch::kFloat32);
+    o.c.kind = 2;
   }
 
   // the tower's backward hands a gradient to torch's optimizer: no optimizer in its dW launch
@@ -935,7 +935,7 @@ class PairPlan : private PlanDict {
   void opt(int mode, double grad_scale) {
     const c10::DeviceGuard g(device());
     TrOptArgs a = dw_.opt;
-    a.grad_scale = static_cast<float>(grad_scale);
+    a.c.grad_scale = static_cast<float>(grad_scale);
     tree_ok(eh_tr_opt(&a, mode, cur_stream()), "pair opt");
   }
   void set_lr(double lr) { dw_.set_lr(lr); }

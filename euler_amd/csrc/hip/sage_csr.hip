@@ -6,7 +6,7 @@
 //   out[m] = act(A[m] @ W^T)                                                         (W [Hp, 2 Dp] bf16 row-major)
 //
 // w_e = cumw[e] - cumw[e - 1] inside its (row, type) segment: the graph stores per-segment
-// prefix sums (the sampler's binary-search operand, sage_tree.hip tr_neighbor), and agg is
+// prefix sums (the sampler's binary-search operand, tree_dev.h tr_neighbor), and agg is
 // the expectation of the sampled mean aggregator.  The denominator is the segments' total
 // weight, as the sampler's: an edge whose neighbour is outside [0, N) keeps its weight there
 // and contributes a zero row (the sampler's -1 draw).

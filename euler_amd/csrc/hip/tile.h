@@ -1,4 +1,5 @@
-// MFMA tile helpers shared by the fused GraphSAGE kernels (sage_tree.hip).
+// MFMA tile helpers shared by the fused GraphSAGE kernels (tree_fwd.hip, tree_head.hip,
+// tree_dw.hip) and the other MFMA units.
 //
 // Two operand layouts make every MFMA operand load a single 16-byte vector:
 //   * "kt" (k-tiled) X_kt[M/32][N][32]: the reduction index m of a weight-gradient
@@ -25,6 +26,16 @@ __device__ __forceinline__ float4_t mfma16(uint4_t a, uint4_t b, float4_t c) {
 // element (m, n) of an [M][N] matrix stored k-tiled
 __device__ __forceinline__ int64_t kt_off(int64_t m, int64_t n, int64_t N) {
   return ((m >> 5) * N + n) * 32 + (m & 31);
+}
+
+// 8 consecutive rows of a column pair (w[i]: the two bf16 of row i) -> the 16-byte kt chunk
+// of each column (row-major tile -> kt copies)
+__device__ __forceinline__ void kt_pack8(const uint32_t (&w)[8], uint4_t& lo, uint4_t& hi) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    lo[i] = (w[2 * i] & 0xffffu) | (w[2 * i + 1] << 16);
+    hi[i] = (w[2 * i] >> 16) | (w[2 * i + 1] & 0xffff0000u);
+  }
 }
 
 // element (n, k) of a weight W[N][K] stored fragment-major

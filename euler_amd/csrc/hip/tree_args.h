@@ -1,6 +1,6 @@
-// Argument blocks of the fused GraphSAGE tree-step kernels (sage_tree.hip), shared by
-// the kernels and the host binding (binding_tree.cpp).  Plain C++ (no device code):
-// the binding TU is compiled by g++.
+// Argument blocks of the fused GraphSAGE tree-step kernels (tree_fwd.hip, tree_head.hip,
+// tree_dw.hip), shared by the kernels and the host binding (binding_tree.cpp).  Plain C++
+// (no device code): the binding TU is compiled by g++.
 //
 // Mini-batch layout ("slotted tree"): level 0 = B roots; every row of level k-1 owns a
 // group of P_k = 2^logP_k slots at level k: slots 0..F_k-1 are its F_k sampled
@@ -205,14 +205,9 @@ struct TrSeg {
   uint16_t* shT;       // optional fm [cols][rows]
   int32_t sgrp;        // vector segments: slab groups per element (1 or 4; tr_seg_layout, tree_plan.h)
 };
-struct TrOptArgs {
-  float *p, *g, *m, *v;
-  uint16_t* g16;  // optional bf16 gradient (data parallel: the all-reduce moves half the bytes);
-                  // mode 0 writes it instead of g, mode 1 reads it
-  int64_t n;
-  TrSeg seg[kTrMaxSegs];
-  int32_t nseg;
-  int32_t nblk;  // blocks of the parameter part of the grid
+// what the optimizer update and the head-statistics reduce read, wherever they run: the
+// optimizer launch (TrOptArgs) or the blocks of a fused dW launch (TrDwOpt)
+struct TrOptCore {
   const int64_t* step;
   float lr, b1, b2, eps, wd, grad_scale;
   int32_t kind;  // 0 adam, 1 adagrad, 2 sgd, 3 momentum
@@ -223,6 +218,16 @@ struct TrOptArgs {
   float* loss_out;         // loss of the last optimizer step
   float* stat_f;           // optional: += the head's second statistic (pair models: reciprocal
                            // ranks) instead of the tp / fp / fn counts
+};
+struct TrOptArgs {
+  float *p, *g, *m, *v;
+  uint16_t* g16;  // optional bf16 gradient (data parallel: the all-reduce moves half the bytes);
+                  // mode 0 writes it instead of g, mode 1 reads it
+  int64_t n;
+  TrSeg seg[kTrMaxSegs];
+  int32_t nseg;
+  int32_t nblk;  // blocks of the parameter part of the grid
+  TrOptCore c;
   TrSampleArgs smp;        // the next step's sampler, run by extra blocks (modes 1/2)
   int32_t nsample;         // sampler blocks (0: none)
   TrFwdArgs gat;           // the next step's layer-0 gather (pipelined step), run by extra blocks:
@@ -250,15 +255,7 @@ struct TrDwOpt {
   int32_t nseg, nblk;
   int32_t rseg0;          // first routed segment of seg[] (== nseg: none)
   TrFoldSeg fseg[kTrMaxProbs];
-  const int64_t* step;
-  float lr, b1, b2, eps, wd, grad_scale;
-  int32_t kind;
-  const float* head_part;
-  int32_t nhead;
-  float* loss_acc;
-  uint32_t* counts;
-  float* loss_out;
-  float* stat_f;
+  TrOptCore c;            // tr_dw_fuse: the optimizer launch's
   // hand-off state, plan-owned, zero between launches; 32 words (one 128-byte line) each:
   // [0] done ticket, [1] status (kTrFuseTimeout), [2 + t] ready counter of routed tile t
   uint32_t* sync;

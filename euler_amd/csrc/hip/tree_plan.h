@@ -1,13 +1,26 @@
 // Host-side planning and validation of the dW launch and the flat-parameter segments of the
-// fused GraphSAGE tree step: split-K plans, block geometry, segment layout and the description
-// of the optimizer inside the dW launch.  Each rule is written once here and read by both the
-// launcher (sage_tree.hip: eh_tr_dw, eh_tr_opt) and the binding (binding_tree.cpp).  Plain
+// fused GraphSAGE tree step: split-K plans, block geometry, segment layout, the description
+// of the optimizer inside the dW launch, and the sampler-argument check of the three launches
+// that carry a sampler.  Each rule is written once here and read by both the launchers
+// (tree_dw.hip: eh_tr_dw, eh_tr_opt; tree_fwd.hip: eh_tr_sample; tree_head.hip: eh_tr_head)
+// and the binding (binding_tree.cpp).  Plain
 // C++17, host only: no torch, no device code, no HIP runtime call, so
 // csrc/tests/tree_plan_selftest.cc checks it on a CPU.
 #pragma once
 #include "hip/tree_args.h"
 
 namespace euler_hip {
+
+// ----------------------------------------------------------------------------- the sampler
+// The sampler blocks of a launch (tr_sample_block: rows_per_block target rows each) can run on
+// a: every array they read or write is set, a leaf fanout, a level the slot chain knows, and
+// nblocks blocks cover the M target rows exactly.
+inline bool tr_sample_ok(const TrSampleArgs& a, int rows_per_block, int64_t nblocks) {
+  if (!a.g.indptr || !a.g.nbr || !a.g.cumw || !a.g.prob || !a.g.alias || !a.tr.rng || !a.roots || !a.nodes || !a.leaf)
+    return false;
+  if (a.FL < 1 || a.lv < 0 || a.lv > 2 || rows_per_block < 1) return false;
+  return nblocks == (a.M + rows_per_block - 1) / rows_per_block;
+}
 
 // ----------------------------------------------------------------------------- split-K plans
 // Stored-G problem (P, Q, MB set): ~target workgroups of 64x64 tiles, at least min_kps 32-row
@@ -26,7 +39,7 @@ inline void tr_plan_stored(TrDwProb& p, int64_t target, int64_t min_kps, bool fo
   p.S = p.F ? 1 : static_cast<int32_t>(slabs);
 }
 
-// routed problems run on kTrRouteP x kTrRouteQ tiles (sage_tree.hip: kRP, kRQ)
+// routed problems run on kTrRouteP x kTrRouteQ tiles (tree_dw.hip: kRP, kRQ)
 constexpr int kTrRouteP = 64, kTrRouteQ = 128;
 inline int32_t tr_route_tiles_q(const TrDwProb& p) { return (p.Q + kTrRouteQ - 1) / kTrRouteQ; }
 inline int32_t tr_route_tiles(const TrDwProb& p) { return (p.P / kTrRouteP) * tr_route_tiles_q(p); }
@@ -133,8 +146,8 @@ inline bool tr_dw_layout(TrDwLaunch& L, TrDwGrid& grid) {
   L.ndw = grid.ndw = L.rwg[L.nroute] + wg;
   if (grid.ndw == 0 || !L.fuse) return true;
   TrDwOpt& o = L.opt;
-  if (L.fuse != 1 || !o.p || !o.m || !o.v || !o.step || !o.loss_acc || !o.loss_out || !o.head_part || o.nhead < 1 ||
-      !o.sync || o.timeout < 1 || o.rseg0 < 0 || o.rseg0 + L.nroute != o.nseg)
+  if (L.fuse != 1 || !o.p || !o.m || !o.v || !o.c.step || !o.c.loss_acc || !o.c.loss_out || !o.c.head_part ||
+      o.c.nhead < 1 || !o.sync || o.timeout < 1 || o.rseg0 < 0 || o.rseg0 + L.nroute != o.nseg)
     return false;
   for (int i = 0; i < pr.n; ++i)
     if (pr.p[i].F < 1 || o.fseg[i].off < 0 || o.fseg[i].off % 4 != 0 || (o.fseg[i].shT && !o.fseg[i].sh)) return false;
@@ -207,22 +220,9 @@ inline bool tr_dw_fuse(const TrDwLaunch& L, const TrOptArgs& o, TrDwOpt& f) {
   f.p = o.p;
   f.m = o.m;
   f.v = o.v;
-  f.step = o.step;
-  f.lr = o.lr;
-  f.b1 = o.b1;
-  f.b2 = o.b2;
-  f.eps = o.eps;
-  f.wd = o.wd;
-  f.grad_scale = o.grad_scale;
-  f.kind = o.kind;
-  f.head_part = o.head_part;
-  f.nhead = o.nhead;
-  f.loss_acc = o.loss_acc;
-  f.counts = o.counts;
-  f.loss_out = o.loss_out;
-  f.stat_f = o.stat_f;
+  f.c = o.c;
   f.timeout = kTrFuseWaitTicks;
-  return o.nhead > 0;
+  return o.c.nhead > 0;
 }
 
 }  // namespace euler_hip

@@ -1,8 +1,10 @@
 // CPU self-test of the dW / optimizer planner (hip/tree_plan.h): split plans, launch geometry,
-// segment layout, the fused-optimizer description and what each of them refuses.  Host code
-// only: no HIP runtime call, nothing to link; pointers are dummies that are never followed.
+// segment layout, the fused-optimizer description, the sampler-argument check and what each of
+// them refuses.  Host code only: no HIP runtime call, nothing to link; pointers are dummies that
+// are never followed.
 // The shapes are those of the GPU tests that pin the same numbers through the plans
 // (tests/test_dw_opt_fuse.py, test_dw_route_pipe.py, test_dw_fold.py), re-derived by hand.
+#include <cstddef>
 #include <cstdio>
 
 #include "hip/tree_plan.h"
@@ -80,10 +82,12 @@ TrOptArgs opt_of(const TrSeg* segs, int n) {
   for (int k = 0; k < n; ++k) o.seg[k] = segs[k];
   o.nseg = n;
   o.nblk = tr_seg_layout(o.seg, n, true);
-  o.step = &step;
-  o.head_part = o.loss_acc = o.loss_out = fbuf;
-  o.nhead = 8;
-  o.counts = ubuf;
+  o.c.step = &step;
+  o.c.head_part = o.c.loss_acc = o.c.loss_out = fbuf;
+  o.c.nhead = 8;
+  o.c.counts = ubuf;
+  o.c.lr = 0.25f;
+  o.c.kind = 3;
   return o;
 }
 
@@ -130,7 +134,66 @@ void test_headline_like() {
   CHECK(f.seg[0].cols == 0 && f.seg[0].blk0 == 0 && f.seg[0].sgrp == 1);
   CHECK(f.seg[1].part == L.route[0].part && f.seg[1].blk0 == 1);
   CHECK(f.fseg[0].off == 65536 && f.fseg[1].off == 196608 && f.fseg[2].off == 213056);
-  CHECK(f.nhead == 8 && f.timeout == kTrFuseWaitTicks && f.step == &step);
+  CHECK(f.c.nhead == 8 && f.timeout == kTrFuseWaitTicks && f.c.step == &step);
+  // the whole core is the optimizer launch's
+  CHECK(f.c.lr == 0.25f && f.c.kind == 3 && f.c.counts == ubuf && f.c.loss_out == fbuf && f.c.stat_f == nullptr);
+  // the core sits where the flat fields sat: both kernels' argument layouts are unchanged
+  static_assert(sizeof(TrOptCore) == 88 && offsetof(TrOptCore, head_part) == 40 && offsetof(TrOptCore, stat_f) == 80,
+                "TrOptCore layout");
+  static_assert(offsetof(TrOptArgs, c) == 56 + sizeof(TrSeg) * kTrMaxSegs, "TrOptArgs layout");
+  static_assert(offsetof(TrOptArgs, smp) == offsetof(TrOptArgs, c) + 88, "TrOptArgs layout");
+  static_assert(offsetof(TrDwOpt, sync) == offsetof(TrDwOpt, c) + 88, "TrDwOpt layout");
+}
+
+// the sampler-argument check of the three launches that carry a sampler
+void test_sampler_args() {
+  static int64_t i64[2];
+  static int32_t i32[8];
+  TrSampleArgs a{};
+  a.g.indptr = i64;
+  a.g.nbr = a.g.alias = i32;
+  a.g.cumw = a.g.prob = fbuf;
+  a.tr.rng = i64;
+  a.roots = i32 + 1;
+  a.nodes = i32 + 2;
+  a.leaf = i32 + 3;
+  a.M = 130;
+  a.lv = 1;
+  a.FL = 10;
+  CHECK(tr_sample_ok(a, 64, 3) && tr_sample_ok(a, 256, 1));  // the optimizer's and the head's sampler blocks
+  CHECK(!tr_sample_ok(a, 64, 2) && !tr_sample_ok(a, 64, 4) && !tr_sample_ok(a, 256, 3) && !tr_sample_ok(a, 0, 3));
+  TrSampleArgs b = a;
+  b.lv = 0;
+  CHECK(tr_sample_ok(b, 64, 3));
+  b.lv = 2;
+  CHECK(tr_sample_ok(b, 64, 3));
+  b.lv = 3;
+  CHECK(!tr_sample_ok(b, 64, 3));
+  b.lv = -1;
+  CHECK(!tr_sample_ok(b, 64, 3));
+  b = a;
+  b.FL = 0;
+  CHECK(!tr_sample_ok(b, 64, 3));
+#define NULLED(field)              \
+  do {                             \
+    b = a;                         \
+    b.field = nullptr;             \
+    CHECK(!tr_sample_ok(b, 64, 3)); \
+  } while (0)
+  NULLED(g.indptr);
+  NULLED(g.nbr);
+  NULLED(g.cumw);
+  NULLED(g.prob);
+  NULLED(g.alias);
+  NULLED(tr.rng);
+  NULLED(roots);
+  NULLED(nodes);
+  NULLED(leaf);
+#undef NULLED
+  // optional arrays stay optional
+  b = a;
+  b.g.root_rows = nullptr, b.tr.root_in = nullptr;
+  CHECK(tr_sample_ok(b, 64, 3));
 }
 
 void test_split_plans() {
@@ -290,7 +353,7 @@ void test_rejections() {
   q.seg[1].off = 65538;  // the fold's 16-byte stores
   CHECK(!tr_dw_fuse(L, q, L.opt));
   q = o;
-  q.nhead = 0;
+  q.c.nhead = 0;
   CHECK(!tr_dw_fuse(L, q, L.opt));
   CHECK(tr_dw_fuse(L, o, L.opt));
 }
@@ -299,6 +362,7 @@ void test_rejections() {
 
 int main() {
   test_headline_like();
+  test_sampler_args();
   test_split_plans();
   test_segments();
   test_two_routed();

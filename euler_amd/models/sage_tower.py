@@ -13,7 +13,7 @@ logits, MRR of the positive as the metric (``utils/metrics.py`` mrr).
 Execution (MI355X), per step, one hipGraph:
   * roots: alias-table sources, the positive neighbour draw and the negatives on the GPU
     (``DeviceGraph.sample_node`` / ``sample_neighbor``, Philox);
-  * layer 0 of each tower is the fused tree step of ``csrc/hip/sage_tree.hip`` over the
+  * layer 0 of each tower is the fused tree step of ``csrc/hip/tree_fwd.hip`` over the
     given roots (``TowerPlan``): hop-1 + leaf sampling, the leaf-row gather + mean, the
     layer-0 MFMA GEMM + ReLU and the tree mean of hop 1 in one launch, producing the last
     conv's input rows [R][2H0]; its backward routes dA1 through the tree and the ReLU bits

@@ -12,7 +12,7 @@ previous hops), trained with adam / adagrad / sgd / momentum (``utils/optimizers
 Execution (MI355X): the graph (CSR + prefix-sum weights), the feature table and the
 labels live in HBM (:meth:`DeviceGraph.from_engine` uploads a loaded dataset;
 :meth:`DeviceGraph.synthetic` builds one on the GPU).  A training step is 4 gfx950
-launches for 2 hops (``csrc/hip/sage_tree.hip``): sampling + gather + GEMM + tree mean,
+launches for 2 hops (``csrc/hip/tree_fwd.hip``, ``tree_head.hip``, ``tree_dw.hip``): sampling + gather + GEMM + tree mean,
 the fused head (last conv, fc, out_fc, loss, backward), the grouped split-K dW with the
 tree routing of the outer layer's gradient built in, and the reduce + optimizer + bf16
 weight shadows.  All state (RNG counter, optimizer step) is on the device, so the step
@@ -880,7 +880,7 @@ class SageTrainer:
 
     def reference_loss_and_grads_bf16(self, params=None, samples=None, table=None):
         """The bf16-aware fp32 oracle of one tree step: the same model, with every operand
-        rounded to bf16 exactly where the fused kernels round it (csrc/hip/sage_tree.hip) and
+        rounded to bf16 exactly where the fused kernels round it (csrc/hip/tree_fwd.hip, tree_head.hip) and
         everything else in fp32 — so the kernels' step must match it to fp32 accumulation
         order (~1e-6), not to bf16 noise.  Rounding points (bf = round to bf16, RNE):
 

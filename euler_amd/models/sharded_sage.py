@@ -1,4 +1,4 @@
-"""The fused GraphSAGE step (models/sage_trainer.py, csrc/hip/sage_tree.hip) over a graph
+"""The fused GraphSAGE step (models/sage_trainer.py, csrc/hip/tree_fwd.hip, tree_head.hip, tree_dw.hip) over a graph
 row-sharded across the data-parallel ranks (graph/sharded_graph.py).
 
 The whole-graph :class:`~euler_amd.models.sage_trainer.SageTrainer` draws each step's

@@ -9,7 +9,7 @@
 with ``w_e = cumw[e] - cumw[e - 1]`` inside its (row, edge type) segment.  ``agg`` is the
 expectation of the sampled mean aggregator of the training path (neighbours drawn with
 replacement, proportionally to edge weight, over the hop's edge-type mask;
-``csrc/hip/sage_tree.hip`` ``tr_neighbor``): with fanout ``F`` the sampled aggregator is
+``csrc/hip/tree_dev.h`` ``tr_neighbor``): with fanout ``F`` the sampled aggregator is
 ``sum / F`` (``(sum + self) / (F + 1)`` with self loops), so ``nbr_scale = F / (F + inc)`` and
 ``self_scale = inc / (F + inc)``.  The denominator is the segments' total weight, as the
 sampler's: a neighbour outside ``[0, N)`` keeps its weight there and contributes a zero row

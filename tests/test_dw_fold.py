@@ -1,4 +1,4 @@
-"""The in-block split-K fold of the stored-G dW problems (csrc/hip/sage_tree.hip
+"""The in-block split-K fold of the stored-G dW problems (csrc/hip/tree_dw.hip
 tr_dw_fold_body; plan key ``dw_fold``).
 
 Every case builds two trainers that differ only in ``dw_fold`` (1: the slabs of a 32x32 tile

@@ -1,4 +1,4 @@
-"""The optimizer inside the dW launch (csrc/hip/sage_tree.hip tr_dw_all_kernel's trailing blocks
+"""The optimizer inside the dW launch (csrc/hip/tree_dw.hip tr_dw_all_kernel's trailing blocks
 and tr_dw_fold_body's update; plan key ``dw_opt_fuse``).
 
 Every case builds two trainers that differ only in ``dw_opt_fuse`` (1: the folded stored-G

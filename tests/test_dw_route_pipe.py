@@ -1,4 +1,4 @@
-"""The pipelined stage loop of the routed layer-0 dW (csrc/hip/sage_tree.hip
+"""The pipelined stage loop of the routed layer-0 dW (csrc/hip/tree_dw.hip
 tr_dw_route_pipe_body; plan key ``dw_route_impl`` = 2, the default).
 
 Every case builds two trainers that differ only in ``EULER_AMD_DW_ROUTE_IMPL`` (2: build, load

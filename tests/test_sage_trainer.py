@@ -1,4 +1,4 @@
-"""SageTrainer (the device-path GraphSAGE trainer, csrc/hip/sage_tree.hip).
+"""SageTrainer (the device-path GraphSAGE trainer, csrc/hip/tree_fwd.hip, tree_head.hip, tree_dw.hip).
 
 GPU: every kernel path (1/2/3 hops, class-id / dense labels, bf16 / fp32 features, self
 loops, multi-type metapaths, odd widths that need padding) against the fp32 torch

@@ -1,6 +1,7 @@
 """The host-side planner of the dW launch and its optimizer (csrc/hip/tree_plan.h): split
-plans, block geometry, segment layout, the fused-optimizer description and their rejections,
-checked on the CPU by csrc/tests/tree_plan_selftest.cc, a stand-alone program built with
+plans, block geometry, segment layout, the fused-optimizer description (one TrOptCore copied
+whole), the sampler-argument check of the three launches that carry a sampler (one case per
+condition it rejects) and their rejections, checked on the CPU by csrc/tests/tree_plan_selftest.cc, a stand-alone program built with
 AddressSanitizer + UBSan.  The plan numbers are the ones the GPU tests pin through the plans
 (test_dw_opt_fuse.py, test_dw_route_pipe.py, test_dw_fold.py)."""
 import os

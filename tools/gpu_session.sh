@@ -231,13 +231,13 @@ for st in "${S[@]}"; do
           python3 benchmarks/bench_deepwalk.py --eval-nodes 0 --mode static --steps 20 --force-dist ;;
     rkb_sweep)
       for v in ${RKB_VALUES:-6 4}; do
-        touch euler_amd/csrc/hip/sage_tree.hip
+        touch euler_amd/csrc/hip/tree_fwd.hip euler_amd/csrc/hip/tree_head.hip euler_amd/csrc/hip/tree_dw.hip
         EULER_AMD_HIP_FLAGS="-DTR_RKB=$v" python -m euler_amd._build > "$OUT/build_rkb$v.log" 2>&1 || exit 4
         run "tree_kernels_rkb$v" 300 python -u tools/tree_kernels.py || exit $?
       done ;;
     bpf_sweep)
       for v in ${BPF_VALUES:-2 4}; do
-        touch euler_amd/csrc/hip/sage_tree.hip
+        touch euler_amd/csrc/hip/tree_fwd.hip euler_amd/csrc/hip/tree_head.hip euler_amd/csrc/hip/tree_dw.hip
         EULER_AMD_HIP_FLAGS="-DTR_FWD_BPF=$v" python -m euler_amd._build > "$OUT/build_bpf$v.log" 2>&1 || exit 4
         run "tree_kernels_bpf$v" 300 python -u tools/tree_kernels.py || exit $?
       done ;;
@@ -248,7 +248,7 @@ for st in "${S[@]}"; do
       i=0
       for v in "${VL[@]}"; do
         i=$((i+1))
-        touch euler_amd/csrc/hip/sage_tree.hip
+        touch euler_amd/csrc/hip/tree_fwd.hip euler_amd/csrc/hip/tree_head.hip euler_amd/csrc/hip/tree_dw.hip
         EULER_AMD_HIP_FLAGS="$v" python -m euler_amd._build > "$OUT/build_variant$i.log" 2>&1 || exit 4
         echo "variant $i: $v" > "$OUT/variant$i.txt"
         if [ "${VARIANT_TESTS:-0}" = 1 ]; then

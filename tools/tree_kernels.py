@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel timing of the SageTrainer step (csrc/hip/sage_tree.hip) at the bench shape.
+"""Per-kernel timing of the SageTrainer step (csrc/hip/tree_fwd.hip, tree_head.hip, tree_dw.hip) at the bench shape.
 
 Times every launch of the step on its own (CUDA events over ``--reps`` back-to-back
 launches) and the whole captured step, and prints the head kernel's per-phase
