@@ -17,6 +17,17 @@ bytes per layer from shapes ((E + M) Dp bytes gathered + M Hp 2 written) and the
 TB/s of the fused layer against the 6.3 TB/s achievable HBM rate.
 
     python benchmarks/bench_sage_infer.py [--num-nodes 10000000] [--reps 3]
+
+``--frontier-ids 1024,65536,1048576`` measures frontier inference instead (``mode="frontier"``,
+nothing of the above runs): for every id count, on a random id subset, the frontier call and
+the all-rows call from a cold cache (``invalidate()`` first: the cost after a training step)
+alternate in one process, ``--reps`` repetitions each after one warm-up.  Per id count the JSON
+line holds the medians and every repetition, the set sizes, the time of building the sets (mark
++ rank + list) against the time of the layers on a prepared plan, and the bytes gathered by
+shape ((edges of the targets + targets) Dp bytes per layer).  The counts are a sweep: the
+``crossover`` entry names the last count at which the frontier call wins and the first at which
+it does not, with the largest set's share of the graph at both — the figure behind
+``frontier_max_fraction`` (which the benchmark itself sets to 1: no fallback hides a time).
 """
 import argparse
 import json
@@ -48,6 +59,8 @@ def main(argv=None):
     ap.add_argument("--sampled-batch", type=int, default=8192)
     ap.add_argument("--skip-composed", action="store_true", help="time the fused layers only (profiling runs)")
     ap.add_argument("--skip-sampled", action="store_true")
+    ap.add_argument("--frontier-ids", default="", help="comma-separated id counts: measure frontier inference "
+                    "against the cold all-rows call at each (module docstring)")
     ap.add_argument("--seed", type=int, default=1234)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -77,6 +90,12 @@ def main(argv=None):
         out = fn()
         torch.cuda.synchronize()
         return time.perf_counter() - t0, out
+
+    if a.frontier_ids:
+        res = frontier_bench(a, g, tr, lw, timed)
+        res["device"] = torch.cuda.get_device_name(0)
+        print(json.dumps(res))
+        return res
 
     prep = None
     prep_s = None
@@ -163,6 +182,84 @@ def main(argv=None):
     res["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(res))
     return res
+
+
+def masked_edges(g, rows, mask):
+    """edges of the valid rows over the masked (row, type) segments, from indptr"""
+    import torch
+
+    r = rows.long()
+    r = r[(r >= 0) & (r < g.num_rows)]
+    n = 0
+    for t in range(g.num_types):
+        if (mask >> t) & 1:
+            n += int((g.indptr[r * g.num_types + t + 1] - g.indptr[r * g.num_types + t]).sum())
+    return n
+
+
+def frontier_bench(a, g, tr, lw, timed):
+    import torch
+
+    from euler_amd.models.sage_infer import FrontierPlan
+
+    N, L = g.num_rows, lw.L
+    if L < 2:
+        raise SystemExit("--frontier-ids needs at least two hops: a 1-hop model has no all-rows pass to avoid")
+    counts = [int(c) for c in a.frontier_ids.split(",")]
+    lw.frontier_max_fraction = 1.0  # measure the frontier path at every count: the sweep finds the crossover
+    perm = torch.randperm(N, generator=torch.Generator().manual_seed(a.seed))
+    widths = [tr.features.shape[1]] + [w.shape[0] for w in lw.conv_weights]
+    esz = tr.features.element_size()
+    points = []
+    for n_ids in counts:
+        rows = perm[: min(n_ids, N)].to(g.device)
+        runs = {
+            "frontier": lambda: lw.embed(rows, mode="frontier"),
+            "all_rows_cold": lambda: (lw.invalidate(), lw.embed(rows))[1],
+            "sets": lambda: FrontierPlan(lw, rows),
+        }
+        times = {name: [] for name in runs}
+        times["layers"] = []
+        for rep in range(a.reps + 1):  # rep 0 warms up; the calls alternate
+            for name, fn in runs.items():
+                t, out = timed(fn)
+                if rep:
+                    times[name].append(t)
+                if name == "sets":
+                    t, y = timed(lambda: lw.embed(rows, mode="frontier", plan=out))
+                    if rep:
+                        times["layers"].append(t)
+                    del y
+                del out
+        plan = FrontierPlan(lw, rows)
+        # targets of layer k: the list of I_{k+1}; of the last layer: the request
+        targets = [s.rows for s in plan.sets] + [rows]
+        gathered = [(masked_edges(g, targets[k], lw.masks[L - 1 - k]) + int(targets[k].numel())) * widths[k] * esz
+                    for k in range(L)]
+        all_rows = [(g.num_edges + N) * widths[k] * esz for k in range(L - 1)] + [gathered[-1]]
+        rec = {"ids": int(rows.numel()), "set_sizes": plan.sizes,
+               "largest_set_fraction": round(max(plan.sizes) / N, 4),
+               "gathered_bytes": gathered, "all_rows_gathered_bytes": all_rows,
+               "gather_work_ratio": round(sum(gathered) / sum(all_rows), 4)}
+        for name, ts in times.items():
+            rec[name + "_ms"] = round(statistics.median(ts) * 1e3, 3)
+            rec[name + "_ms_all"] = [round(t * 1e3, 3) for t in ts]
+        rec["frontier_over_all_rows_cold"] = round(rec["frontier_ms"] / rec["all_rows_cold_ms"], 4)
+        points.append(rec)
+        del plan, targets
+        torch.cuda.empty_cache()
+    wins = [p for p in points if p["frontier_ms"] < p["all_rows_cold_ms"]]
+    loses = [p for p in points if p["frontier_ms"] >= p["all_rows_cold_ms"]]
+    cross = {"last_win": None, "first_loss": None}
+    if wins:
+        w = max(wins, key=lambda p: p["ids"])
+        cross["last_win"] = {"ids": w["ids"], "largest_set_fraction": w["largest_set_fraction"]}
+    if loses:
+        lo = min(loses, key=lambda p: p["ids"])
+        cross["first_loss"] = {"ids": lo["ids"], "largest_set_fraction": lo["largest_set_fraction"]}
+    return {"bench": "sage_infer_frontier", "num_nodes": N, "num_edges": g.num_edges, "fanouts": list(lw.fanouts),
+            "feature_dim": a.feature_dim, "hidden_dim": a.hidden_dim, "reps": a.reps, "points": points,
+            "crossover": cross}
 
 
 if __name__ == "__main__":

@@ -539,6 +539,8 @@ PYBIND11_MODULE(_hip_ops, m) {
   register_kg_rank_ops(m);
   register_sage_csr_ops(m);
   register_graph_build_ops(m);
+  auto f = m.def_submodule("frontier");
+  register_frontier_ops(f);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

@@ -43,6 +43,9 @@ void register_kg_rank_ops(py::module& m);
 void register_sage_csr_ops(py::module& m);
 // binding_graph_build.cpp: edge list -> device CSR (DeviceGraph.from_edges)
 void register_graph_build_ops(py::module& m);
+// binding_frontier.cpp: row sets of frontier inference and the layer over a set's compact table
+// (registered on the submodule _hip_ops.frontier)
+void register_frontier_ops(py::module& m);
 
 namespace euler_bind {
 

@@ -244,6 +244,29 @@ hipError_t eh_sage_csr_fwd(const int64_t* indptr, const int32_t* nbr, const floa
                            uint32_t mask, const void* x, int x_fp32, int Dp, const int32_t* rows, int64_t M,
                            const void* W, int Hp, float nbr_scale, float self_scale, int relu, void* out,
                            int out_fp32, hipStream_t s);
+// the same layer on a compact table: x [count, Dp] holds the rows of a set in list order and is
+// addressed through the set's rank bitmap set_words (csr_rowset.h), for neighbour rows and the
+// self row alike.  A graph row the set lacks is never read: a zero row, and one more in
+// *missing (int32 [1]; the caller zeroes it and reads it after the launch)
+hipError_t eh_sage_csr_fwd_mapped(const int64_t* indptr, const int32_t* nbr, const float* cumw, int64_t N, int64_t E,
+                                  int T, uint32_t mask, const void* x, int x_fp32, int Dp, const int32_t* set_words,
+                                  int64_t count, int32_t* missing, const int32_t* rows, int64_t M, const void* W,
+                                  int Hp, float nbr_scale, float self_scale, int relu, void* out, int out_fp32,
+                                  hipStream_t s);
+
+// frontier.hip (row sets as rank bitmaps: words int32 [eh_frontier_words(N), 2] = (bits, set
+// bits before the word), csr_rowset.h).  N in [1, 2^31)
+int64_t eh_frontier_words(int64_t N);
+int64_t eh_frontier_scan_blocks(int64_t N);  // entries of eh_frontier_rank's scratch
+// set the bits of rows [n] / of their neighbours over the masked segments; entries and
+// neighbours outside [0, N) are ignored
+hipError_t eh_frontier_mark(int32_t* words, int64_t N, const int32_t* rows, int64_t n, hipStream_t s);
+hipError_t eh_frontier_mark_neighbors(int32_t* words, const int64_t* indptr, const int32_t* nbr, int64_t N, int64_t E,
+                                      int T, uint32_t mask, const int32_t* rows, int64_t n, hipStream_t s);
+// fills the rank column; *count = number of set bits; totals: int32 scratch
+hipError_t eh_frontier_rank(int32_t* words, int64_t N, int32_t* totals, int32_t* count, hipStream_t s);
+// list [count]: the set's rows, ascending (after eh_frontier_rank)
+hipError_t eh_frontier_list(const int32_t* words, int64_t N, int64_t count, int32_t* list, hipStream_t s);
 
 // kg_rank.hip (link-prediction rank counts: every query row against every candidate row, no
 // [B, N] score matrix).  kind 0 = l1, 1 = squared l2 (lower is better), 2 = dot (higher is

@@ -25,6 +25,13 @@
 //            fragment as B), so a lane's four accumulators are four consecutive output columns
 //            of one row: one 8-byte (bf16) or 16-byte (fp32) store.
 // No atomics: two launches on the same inputs are bit-identical.
+//
+// The table x either has one row per graph row (RowIdentity) or holds the rows of a row set in
+// list order and is addressed through the set's rank bitmap (RowRank, csr_rowset.h): the
+// row -> table-position step is a template functor, everything else is the same code, so the
+// two give the same bits for the same input rows.  A row the set lacks is never read: it counts
+// as a zero row and is reported through a status word (the only atomic, on the error path).
+#include "hip/csr_rowset.h"
 #include "hip/tile.h"
 
 namespace euler_hip {
@@ -33,7 +40,6 @@ constexpr int kCsrBM = 64;
 constexpr int kCsrThreads = 512;
 constexpr int kCsrWaves = kCsrThreads / 64;
 constexpr int kCsrUnroll = 2;
-constexpr int kCsrHubDeg = 256;  // more edges than this: the whole block gathers the row
 constexpr int kCsrMaxD = 512;
 
 struct CsrGraph {
@@ -68,9 +74,10 @@ __device__ __forceinline__ void csr_load8(const float* p, float* v) {
 // this lane group's share (edges slot, slot + nslots, ...) of row's masked segments:
 // acc[8] += (w_e / tot) * x[nbr_e][8c .. 8c + 7] — the row of the row-normalised adjacency, edge
 // by edge (tot > 0: rows without weight are not gathered)
-template <typename XT>
-__device__ __forceinline__ void csr_accum(const CsrGraph& g, const XT* __restrict__ x, int Dp, int64_t row, float tot,
-                                          int slot, int nslots, int c, bool lane_on, float* acc) {
+template <typename XT, typename MAP>
+__device__ __forceinline__ void csr_accum(const CsrGraph& g, const XT* __restrict__ x, const MAP& pos_of, int Dp,
+                                          int64_t row, float tot, int slot, int nslots, int c, bool lane_on,
+                                          float* acc) {
   const int64_t base = row * g.T;
   for (int t = 0; t < g.T; ++t) {
     if (!((g.mask >> t) & 1u)) continue;
@@ -93,9 +100,13 @@ __device__ __forceinline__ void csr_accum(const CsrGraph& g, const XT* __restric
       }
 #pragma unroll
       for (int u = 0; u < kCsrUnroll; ++u) {
+        // the neighbour's row of x: graph row j itself, or its position in a row set's table
+        // (csr_rowset.h; -1: the set lacks the row, which then reads nothing)
         const bool ok = lane_on && j[u] >= 0 && static_cast<int64_t>(j[u]) < g.N;
-        if (ok) {
-          csr_load8(x + static_cast<int64_t>(j[u]) * Dp + c * 8, v[u]);
+        int64_t p = -1;
+        if (ok) p = pos_of(static_cast<int64_t>(j[u]));
+        if (MAP::found(ok, p)) {
+          csr_load8(x + p * Dp + c * 8, v[u]);
         } else {
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[u][i] = 0.f;
@@ -112,19 +123,25 @@ __device__ __forceinline__ void csr_accum(const CsrGraph& g, const XT* __restric
 
 // the A-tile row of one target: [ x_self | nbr_scale * acc + self_scale * x_self ], every
 // product and the sum rounded to fp32 on its own (no fma contraction: the documented order)
-template <typename XT>
-__device__ __forceinline__ void csr_finish(const XT* __restrict__ x, int Dp, int64_t row, const float* acc,
-                                           float nbr_scale, float self_scale, bf16_t* arow, int c) {
+template <typename XT, typename MAP>
+__device__ __forceinline__ void csr_finish(const XT* __restrict__ x, const MAP& pos_of, int Dp, int64_t row,
+                                           const float* acc, float nbr_scale, float self_scale, bf16_t* arow, int c) {
   float xs[8], o[8];
-  csr_load8(x + row * Dp + c * 8, xs);
+  const int64_t p = pos_of(row);
+  if (MAP::found(true, p)) {
+    csr_load8(x + p * Dp + c * 8, xs);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xs[i] = 0.f;
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) o[i] = __fadd_rn(__fmul_rn(nbr_scale, acc[i]), __fmul_rn(self_scale, xs[i]));
   *reinterpret_cast<uint4_t*>(arow + c * 8) = pack_bf16x8(xs);
   *reinterpret_cast<uint4_t*>(arow + Dp + c * 8) = pack_bf16x8(o);
 }
 
-template <typename XT>
-__device__ __forceinline__ void csr_gather_tile(const CsrGraph& g, const XT* __restrict__ x, int Dp,
+template <typename XT, typename MAP>
+__device__ __forceinline__ void csr_gather_tile(const CsrGraph& g, const XT* __restrict__ x, const MAP& pos_of, int Dp,
                                                 const int32_t* __restrict__ rows, int64_t M, int64_t row0,
                                                 float nbr_scale, float self_scale, bf16_t* lds, int ldsw, float* part,
                                                 int32_t* m_row, int32_t* m_deg, float* m_tot) {
@@ -181,13 +198,13 @@ __device__ __forceinline__ void csr_gather_tile(const CsrGraph& g, const XT* __r
     for (int q = 0; q < 8; ++q) acc[q] = 0.f;
     const float tot = m_tot[p];
     if (deg > 0 && tot > 0.f) {
-      csr_accum(g, x, Dp, r, tot, grp, ng, c, lane_on, acc);
+      csr_accum(g, x, pos_of, Dp, r, tot, grp, ng, c, lane_on, acc);
       for (int o = lpr; o < 64; o <<= 1) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc[q] += __shfl_xor(acc[q], o, 64);
       }
     }
-    if (grp == 0 && lane_on) csr_finish(x, Dp, r, acc, nbr_scale, self_scale, arow, c);
+    if (grp == 0 && lane_on) csr_finish(x, pos_of, Dp, r, acc, nbr_scale, self_scale, arow, c);
   }
 
   // phase 1b: hub targets, all waves on one row (block-uniform loop: m_deg is in LDS)
@@ -198,7 +215,7 @@ __device__ __forceinline__ void csr_gather_tile(const CsrGraph& g, const XT* __r
 #pragma unroll
     for (int q = 0; q < 8; ++q) acc[q] = 0.f;
     const float tot = m_tot[p];
-    if (tot > 0.f) csr_accum(g, x, Dp, r, tot, wave * ng + grp, kCsrWaves * ng, c, lane_on, acc);
+    if (tot > 0.f) csr_accum(g, x, pos_of, Dp, r, tot, wave * ng + grp, kCsrWaves * ng, c, lane_on, acc);
     for (int o = lpr; o < 64; o <<= 1) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) acc[q] += __shfl_xor(acc[q], o, 64);
@@ -215,7 +232,7 @@ __device__ __forceinline__ void csr_gather_tile(const CsrGraph& g, const XT* __r
         s[q] = part[c * 8 + q];
         for (int w = 1; w < kCsrWaves; ++w) s[q] += part[w * Dp + c * 8 + q];
       }
-      csr_finish(x, Dp, r, s, nbr_scale, self_scale, lds + p * ldsw, c);
+      csr_finish(x, pos_of, Dp, r, s, nbr_scale, self_scale, lds + p * ldsw, c);
     }
     __syncthreads();
   }
@@ -282,9 +299,9 @@ __device__ __forceinline__ void csr_gemm_tile(const bf16_t* lds, int ldsw, int K
   }
 }
 
-template <int BN, typename XT, typename OT>
-__global__ __launch_bounds__(kCsrThreads) void sage_csr_fwd_kernel(CsrGraph g, const XT* __restrict__ x, int Dp,
-                                                                  const int32_t* __restrict__ rows, int64_t M,
+template <int BN, typename XT, typename OT, typename MAP>
+__global__ __launch_bounds__(kCsrThreads) void sage_csr_fwd_kernel(CsrGraph g, const XT* __restrict__ x, MAP pos_of,
+                                                                  int Dp, const int32_t* __restrict__ rows, int64_t M,
                                                                   const bf16_t* __restrict__ W, int H,
                                                                   float nbr_scale, float self_scale, int relu,
                                                                   OT* __restrict__ out) {
@@ -297,7 +314,7 @@ __global__ __launch_bounds__(kCsrThreads) void sage_csr_fwd_kernel(CsrGraph g, c
   const int64_t tiles = ceil_div(M, kCsrBM);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t row0 = tile * kCsrBM;
-    csr_gather_tile(g, x, Dp, rows, M, row0, nbr_scale, self_scale, lds, ldsw, part, m_row, m_deg, m_tot);
+    csr_gather_tile(g, x, pos_of, Dp, rows, M, row0, nbr_scale, self_scale, lds, ldsw, part, m_row, m_deg, m_tot);
     __syncthreads();
     csr_gemm_tile<BN>(lds, ldsw, 2 * Dp, W, H, M, row0, relu, out);
     __syncthreads();  // the next tile overwrites the A tile and the metadata
@@ -315,28 +332,47 @@ size_t csr_lds_bytes(int Dp) {
          static_cast<size_t>(kCsrBM) * 12;
 }
 
-template <int BN, typename XT, typename OT>
-hipError_t csr_launch(const CsrGraph& g, const void* x, int Dp, const int32_t* rows, int64_t M, const void* W, int H,
-                      float nbr_scale, float self_scale, int relu, void* out, hipStream_t s) {
+template <int BN, typename XT, typename OT, typename MAP>
+hipError_t csr_launch(const CsrGraph& g, const void* x, const MAP& pos_of, int Dp, const int32_t* rows, int64_t M,
+                      const void* W, int H, float nbr_scale, float self_scale, int relu, void* out, hipStream_t s) {
   const size_t lds = csr_lds_bytes(Dp);
-  auto* k = sage_csr_fwd_kernel<BN, XT, OT>;
+  auto* k = sage_csr_fwd_kernel<BN, XT, OT, MAP>;
   if (lds > 65536)
     EULER_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         static_cast<int>(lds)));
   const int64_t tiles = ceil_div(M, kCsrBM);
   const dim3 grid(static_cast<uint32_t>(tiles < kMaxGridBlocks ? tiles : kMaxGridBlocks));
-  hipLaunchKernelGGL(k, grid, dim3(kCsrThreads), lds, s, g, static_cast<const XT*>(x), Dp, rows, M,
+  hipLaunchKernelGGL(k, grid, dim3(kCsrThreads), lds, s, g, static_cast<const XT*>(x), pos_of, Dp, rows, M,
                      static_cast<const bf16_t*>(W), H, nbr_scale, self_scale, relu, static_cast<OT*>(out));
   return hipGetLastError();
 }
 
-template <typename XT, typename OT>
-hipError_t csr_pick_bn(const CsrGraph& g, const void* x, int Dp, const int32_t* rows, int64_t M, const void* W, int H,
-                       float nbr_scale, float self_scale, int relu, void* out, hipStream_t s) {
+template <typename XT, typename OT, typename MAP>
+hipError_t csr_pick_bn(const CsrGraph& g, const void* x, const MAP& pos_of, int Dp, const int32_t* rows, int64_t M,
+                       const void* W, int H, float nbr_scale, float self_scale, int relu, void* out, hipStream_t s) {
   // 128 columns per pass (two passes at H = 256): a 256-column pass needs more than the 128
   // registers of 4 waves per SIMD, and the gather's rate is set by the waves in flight
-  if (H > 64) return csr_launch<128, XT, OT>(g, x, Dp, rows, M, W, H, nbr_scale, self_scale, relu, out, s);
-  return csr_launch<64, XT, OT>(g, x, Dp, rows, M, W, H, nbr_scale, self_scale, relu, out, s);
+  if (H > 64) return csr_launch<128, XT, OT>(g, x, pos_of, Dp, rows, M, W, H, nbr_scale, self_scale, relu, out, s);
+  return csr_launch<64, XT, OT>(g, x, pos_of, Dp, rows, M, W, H, nbr_scale, self_scale, relu, out, s);
+}
+
+// pos_of: where x keeps a graph row (RowIdentity: x has every row; RowRank: a set's table)
+template <typename MAP>
+hipError_t csr_dispatch(const CsrGraph& g, const void* x, int x_fp32, const MAP& pos_of, int Dp, const int32_t* rows,
+                        int64_t M, const void* W, int Hp, float nbr_scale, float self_scale, int relu, void* out,
+                        int out_fp32, hipStream_t s) {
+  if (M == 0) return hipSuccess;
+  if (Dp <= 0 || Dp % 16 != 0 || Dp > kCsrMaxD || Hp <= 0 || Hp % 64 != 0 || g.T < 1 || g.T > 32 || g.N < 0 ||
+      g.E < 0 || M < 0)
+    return hipErrorInvalidValue;
+  if (x_fp32) {
+    if (out_fp32)
+      return csr_pick_bn<float, float>(g, x, pos_of, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
+    return csr_pick_bn<float, bf16_t>(g, x, pos_of, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
+  }
+  if (out_fp32)
+    return csr_pick_bn<bf16_t, float>(g, x, pos_of, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
+  return csr_pick_bn<bf16_t, bf16_t>(g, x, pos_of, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
 }
 
 }  // namespace
@@ -349,17 +385,19 @@ hipError_t eh_sage_csr_fwd(const int64_t* indptr, const int32_t* nbr, const floa
                            uint32_t mask, const void* x, int x_fp32, int Dp, const int32_t* rows, int64_t M,
                            const void* W, int Hp, float nbr_scale, float self_scale, int relu, void* out,
                            int out_fp32, hipStream_t s) {
-  if (M == 0) return hipSuccess;
-  if (Dp <= 0 || Dp % 16 != 0 || Dp > kCsrMaxD || Hp <= 0 || Hp % 64 != 0 || T < 1 || T > 32 || N < 0 || E < 0 ||
-      M < 0)
-    return hipErrorInvalidValue;
   const CsrGraph g{indptr, nbr, cumw, N, E, T, mask};
-  if (x_fp32) {
-    if (out_fp32) return csr_pick_bn<float, float>(g, x, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
-    return csr_pick_bn<float, bf16_t>(g, x, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
-  }
-  if (out_fp32) return csr_pick_bn<bf16_t, float>(g, x, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
-  return csr_pick_bn<bf16_t, bf16_t>(g, x, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, s);
+  return csr_dispatch(g, x, x_fp32, RowIdentity{}, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, out_fp32, s);
+}
+
+hipError_t eh_sage_csr_fwd_mapped(const int64_t* indptr, const int32_t* nbr, const float* cumw, int64_t N, int64_t E,
+                                  int T, uint32_t mask, const void* x, int x_fp32, int Dp, const int32_t* set_words,
+                                  int64_t count, int32_t* missing, const int32_t* rows, int64_t M, const void* W,
+                                  int Hp, float nbr_scale, float self_scale, int relu, void* out, int out_fp32,
+                                  hipStream_t s) {
+  if (count < 0 || count > N || set_words == nullptr || missing == nullptr) return hipErrorInvalidValue;
+  const CsrGraph g{indptr, nbr, cumw, N, E, T, mask};
+  const RowRank pos_of{reinterpret_cast<const rs_uint2*>(set_words), static_cast<int32_t>(count), reinterpret_cast<uint32_t*>(missing)};
+  return csr_dispatch(g, x, x_fp32, pos_of, Dp, rows, M, W, Hp, nbr_scale, self_scale, relu, out, out_fp32, s);
 }
 
 }  // extern "C"

@@ -881,30 +881,37 @@ class BaseEstimator:
                 yield None, {"pad_to": pad}
 
     def _infer_mode(self) -> str:
-        """``params["infer_mode"]``: "sampled" (default: a fresh sampled tree per root) or
-        "layerwise" (deterministic full-neighbourhood inference, models/sage_infer.py)"""
+        """``params["infer_mode"]``: "sampled" (default: a fresh sampled tree per root),
+        "layerwise" (deterministic full-neighbourhood inference, models/sage_infer.py) or
+        "frontier" (the same embeddings, computed over only the rows the ids reach)"""
         mode = self.params.get("infer_mode") or "sampled"
-        if mode not in ("sampled", "layerwise"):
-            raise ValueError(f"infer_mode must be 'sampled' or 'layerwise', got {mode!r}")
+        if mode not in ("sampled", "layerwise", "frontier"):
+            raise ValueError(f"infer_mode must be 'sampled', 'layerwise' or 'frontier', got {mode!r}")
         return mode
 
     def _layerwise_trainer(self):
-        """the device trainer of ``infer_mode="layerwise"``; never a fallback: a ValueError
-        names why this estimator has none"""
+        """the device trainer of ``infer_mode="layerwise"`` / ``"frontier"``; never a fallback: a
+        ValueError names why this estimator has none"""
+        mode = self._infer_mode()
         if not self.params.get("device_graph"):
-            raise ValueError("infer_mode='layerwise' runs on the HBM graph: set device_graph=True")
+            raise ValueError(f"infer_mode={mode!r} runs on the HBM graph: set device_graph=True")
         if self.params.get("device_infer", True) is False:
-            raise ValueError("infer_mode='layerwise' is device inference: device_infer=False turns it off")
+            raise ValueError(f"infer_mode={mode!r} is device inference: device_infer=False turns it off")
         tr = self._device_inference_trainer()
         if tr is None:
-            raise ValueError(f"infer_mode='layerwise': {type(self.model).__name__} has no device inference trainer "
+            raise ValueError(f"infer_mode={mode!r}: {type(self.model).__name__} has no device inference trainer "
                              "(layer-wise inference covers SupervisedGraphSage on an unsharded device graph)")
-        if not callable(getattr(tr, "infer_logits_layerwise", None)) or \
-                not callable(getattr(tr, "infer_embed_layerwise", None)):
-            raise ValueError(f"infer_mode='layerwise': {type(tr).__name__} has no layer-wise inference (it covers "
+        if not callable(getattr(tr, "infer_logits_" + mode, None)) or \
+                not callable(getattr(tr, "infer_embed_" + mode, None)):
+            raise ValueError(f"infer_mode={mode!r}: {type(tr).__name__} has no layer-wise inference (it covers "
                              "SageTrainer on an unsharded device graph; sharded, GCN-family and unsupervised "
                              "trainers infer with infer_mode='sampled')")
         return tr
+
+    def _infer_fn(self, tr, what):
+        """``tr.infer_logits`` / ``tr.infer_embed`` (``what``) of the estimator's ``infer_mode``"""
+        mode = self._infer_mode()
+        return getattr(tr, f"infer_{what}" if mode == "sampled" else f"infer_{what}_{mode}")
 
     def _device_evaluate(self, tr):
         """loss and the model's streaming metric over the eval id batches, every batch's
@@ -917,7 +924,7 @@ class BaseEstimator:
         name = getattr(self.model, "metric_name", getattr(tr, "metric_name", "f1"))
         losses, res, steps, n, t0 = [], {}, 0, 0, time.time()
         extract = lambda b: self.get_evaluate_from_input(b, self.params)  # noqa: E731
-        infer_logits = tr.infer_logits_layerwise if self._infer_mode() == "layerwise" else tr.infer_logits
+        infer_logits = self._infer_fn(tr, "logits")
         for src, kw in self._lockstep_batches(tr, self._eval_batches(), extract, self.evaluate_stop_onetime):
             if src is None:  # a padding batch of the collective loop
                 tr.infer_logits(torch.zeros(0, dtype=torch.int64), **kw)
@@ -942,7 +949,7 @@ class BaseEstimator:
         ids_out, emb_out = [], []
         n, t0 = 0, time.time()
         extract = lambda b: self.get_infer_from_input(b, self.params)  # noqa: E731
-        infer_embed = tr.infer_embed_layerwise if self._infer_mode() == "layerwise" else tr.infer_embed
+        infer_embed = self._infer_fn(tr, "embed")
         for src, kw in self._lockstep_batches(tr, self.infer_input_fn(), extract):
             if src is None:  # a padding batch of the collective loop
                 tr.infer_embed(torch.zeros(0, dtype=torch.int64), **kw)
@@ -971,7 +978,7 @@ class BaseEstimator:
 
     @torch.no_grad()
     def evaluate(self):
-        tr = self._layerwise_trainer() if self._infer_mode() == "layerwise" else self._device_inference_trainer()
+        tr = self._device_inference_trainer() if self._infer_mode() == "sampled" else self._layerwise_trainer()
         if tr is not None and callable(getattr(tr, "infer_logits", None)):
             res = self._device_evaluate(tr)
             if res is not None:
@@ -1008,7 +1015,7 @@ class BaseEstimator:
 
     @torch.no_grad()
     def infer(self):
-        tr = self._layerwise_trainer() if self._infer_mode() == "layerwise" else self._device_inference_trainer()
+        tr = self._device_inference_trainer() if self._infer_mode() == "sampled" else self._layerwise_trainer()
         if tr is not None and callable(getattr(tr, "infer_embed", None)):
             out = self._device_infer(tr)
             if out is not None:

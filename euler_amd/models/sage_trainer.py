@@ -835,6 +835,18 @@ class SageTrainer:
     def infer_embed_layerwise(self, ids):
         return self.infer_logits_layerwise(ids)[0]
 
+    @torch.no_grad()
+    def infer_logits_frontier(self, ids):
+        """:meth:`infer_logits_layerwise` over only the rows the ids reach (their k-hop frontier,
+        ``LayerwiseSageInference`` ``mode="frontier"``): the same bits, no all-rows table, a
+        cost that follows the request.  Same tuple and id handling."""
+        rows = self.graph.rows_of(ids).to(self.graph.device)
+        emb, logits = self.layerwise().logits(rows.clamp(min=0), mode="frontier")
+        return emb, logits, self._labels_of(rows.clamp(min=0)).to(emb.device)
+
+    def infer_embed_frontier(self, ids):
+        return self.infer_logits_frontier(ids)[0]
+
     def logical_forward(self, params, roots, nodes, leaf, table=None):
         """fp32 logits of the model for one sampled slotted tree (``table``: the feature rows
         ``nodes`` / ``leaf`` index; default the whole feature table)"""

@@ -38,9 +38,11 @@ class ShardedSageTrainer(SageTrainer):
     # padded size in lockstep (estimator/base.py _lockstep_batches)
     collective_infer = True
     # layer-wise inference walks one whole CSR and feature table: a row-sharded graph has
-    # neither (estimator infer_mode="layerwise" reports that instead of falling back)
+    # neither (estimator infer_mode="layerwise" / "frontier" report that instead of falling back)
     infer_logits_layerwise = None
     infer_embed_layerwise = None
+    infer_logits_frontier = None
+    infer_embed_frontier = None
 
     def __init__(self, graph, batch_size, fanouts, dims, label_dim, **kw):
         self.sgraph = graph

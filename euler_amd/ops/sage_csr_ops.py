@@ -21,6 +21,10 @@ the same maths from existing pieces: per-edge normalised weights from ``cumw``, 
 (``spmm_csr``; ``index_add_`` on the CPU) and ``gnn_ops.gemm``.  It is the CPU path and the
 A/B baseline on the GPU.  Its A operand has ``weight``'s dtype: bf16 weights round A to bf16
 where the kernel does, fp32 weights (the CPU model path) keep the whole layer in fp32.
+
+With ``x_set`` (``ops/frontier_ops.RowSet``) ``x`` holds only the rows of a set, in list order,
+and is addressed through the set's rank bitmap: the same layer, the same bits, for callers
+that computed only the rows a request reaches (``models/sage_infer.py`` ``mode="frontier"``).
 """
 from __future__ import annotations
 
@@ -132,23 +136,56 @@ def _composed(graph, x, weight, mask, rows, nbr_scale, self_scale, relu, out_dty
     return y.to(out_dtype)
 
 
+def _remapped(c: ComposedCSR, x_set) -> ComposedCSR:
+    """the composed operands with ``col`` / ``src`` as positions in ``x_set``'s compact table;
+    a row the set lacks that carries weight is refused, as the kernel refuses it"""
+    col, src = x_set.positions(c.col), x_set.positions(c.src)
+    # composed_csr points weightless edges (a neighbour outside the graph) and absent targets at row 0
+    lacks = (int(((col < 0) & (c.w != 0)).sum()) if col.numel() else 0) + int(((src < 0) & c.valid).sum())
+    if lacks:
+        raise RuntimeError(f"sage_csr_layer(x_set=...): the row set lacks {lacks} of the rows the layer reads "
+                           "(x_set must hold the targets and their masked neighbours)")
+    return ComposedCSR(c.indptr, col.clamp(min=0), c.w, src.clamp(min=0), c.valid, False)
+
+
 def sage_csr_layer(graph, x, weight, mask=None, rows=None, nbr_scale=1.0, self_scale=0.0, relu=True,
-                   out_dtype=torch.bfloat16, impl="fused", out=None, prepared=None):
+                   out_dtype=torch.bfloat16, impl="fused", out=None, prepared=None, x_set=None):
     """One full-neighbourhood GraphSAGE layer (module docstring).  ``x`` [N, Dp] bf16 / fp32
     with one row per graph row, ``weight`` [Hp, 2 Dp], ``mask`` an edge-type bit set (None:
     every type), ``rows`` int [M] (None: every row; duplicates allowed).  ``impl="fused"``
     needs a GPU graph, Dp % 16 == 0, Hp % 64 == 0 and a bf16 ``weight``; ``out`` (fused only)
-    is an optional [M, Hp] destination, ``prepared`` (composed only) a :func:`composed_csr`."""
+    is an optional [M, Hp] destination, ``prepared`` (composed only) a :func:`composed_csr`.
+
+    With ``x_set`` (a :class:`~euler_amd.ops.frontier_ops.RowSet`) ``x`` is the compact table
+    ``[x_set.count, Dp]`` of the set's rows in list order; the set must hold the targets and
+    their masked neighbours (``neighbor_closure``).  The result has the same bits as the call
+    on the full table holding the same rows (fused: the same kernel code addressed through the
+    set's rank bitmap; composed, CPU graphs only: ``col`` / ``src`` remapped).  A row the layer
+    reads that the set lacks is never read: a ``RuntimeError``."""
     if impl not in ("fused", "composed"):
         raise ValueError("impl must be 'fused' or 'composed'")
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
-    if x.dim() != 2 or x.shape[0] != graph.num_rows:
+    if x_set is not None:
+        if x_set.num_rows != graph.num_rows:
+            raise ValueError(f"x_set covers {x_set.num_rows} rows, the graph has {graph.num_rows}")
+        if x.dim() != 2 or x.shape[0] != x_set.count:
+            raise ValueError(f"x must be [x_set.count = {x_set.count}, D], got {tuple(x.shape)}")
+    elif x.dim() != 2 or x.shape[0] != graph.num_rows:
         raise ValueError(f"x must be [num_rows = {graph.num_rows}, D], got {tuple(x.shape)}")
     if weight.dim() != 2 or weight.shape[1] != 2 * x.shape[1]:
         raise ValueError(f"weight must be [H, 2 D = {2 * x.shape[1]}], got {tuple(weight.shape)}")
     m = graph._mask(None) if mask is None else int(mask)
     if impl == "composed":
+        if x_set is not None:
+            if use_hip(graph.indptr):
+                raise ValueError("sage_csr_layer(impl='composed', x_set=...) is the CPU path; a GPU graph takes "
+                                 "impl='fused'")
+            if prepared is not None:
+                raise ValueError("prepared operands index the full table: not with x_set")
+            prepared = _remapped(composed_csr(graph, m, rows, nbr_scale, self_scale), x_set)
+            if x.shape[0] == 0:  # every target is outside the graph: zero rows out of a zero row
+                x = x.new_zeros((1, x.shape[1]))
         y = _composed(graph, x, weight, m, rows, nbr_scale, self_scale, relu, out_dtype, prepared)
         if out is not None:
             out.copy_(y)
@@ -160,5 +197,15 @@ def sage_csr_layer(graph, x, weight, mask=None, rows=None, nbr_scale=1.0, self_s
     r = None
     if rows is not None:
         r = rows.to(device=x.device, dtype=torch.int32).reshape(-1).contiguous()
+    if x_set is not None:
+        missing = torch.zeros(1, dtype=torch.int32, device=x.device)
+        y = hip().frontier.sage_csr_fwd_mapped(graph.indptr, graph.nbr, graph.cumw, graph.num_types, m & 0xFFFFFFFF, x,
+                                               x_set.table, x_set.count, missing, weight, r, float(nbr_scale),
+                                               float(self_scale), bool(relu), out_dtype == torch.float32, out)
+        lacks = int(missing.item())
+        if lacks:
+            raise RuntimeError(f"sage_csr_fwd_mapped: the row set lacks rows the layer reads ({lacks} reads refused; "
+                               "x_set must hold the targets and their masked neighbours)")
+        return y
     return hip().sage_csr_fwd(graph.indptr, graph.nbr, graph.cumw, graph.num_types, m & 0xFFFFFFFF, x, weight, r,
                               float(nbr_scale), float(self_scale), bool(relu), out_dtype == torch.float32, out)

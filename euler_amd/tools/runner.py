@@ -239,10 +239,12 @@ def parse_args(argv=None, model=None):
                         "(shard_idx = rank): host memory per rank is 1/W of the graph (training only: "
                         "an engine-path evaluate would see one shard)")
     p.add_argument("--device_feature_dtype", default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--infer_mode", default="sampled", choices=["sampled", "layerwise"],
-                   help="with --device_graph, evaluate / infer: a fresh sampled tree per root (sampled) or "
+    p.add_argument("--infer_mode", default="sampled", choices=["sampled", "layerwise", "frontier"],
+                   help="with --device_graph, evaluate / infer: a fresh sampled tree per root (sampled), "
                         "deterministic layer-wise full-neighbourhood inference on the fused CSR-mean kernel "
-                        "(layerwise; graphsage: models/sage_infer.py)")
+                        "(layerwise; graphsage: models/sage_infer.py), or the same embeddings computed over "
+                        "only the rows the ids reach (frontier: for a few ids of a large graph; a whole-graph "
+                        "infer is cheaper with layerwise)")
     p.add_argument("--cuda_graph", default="auto", choices=["auto", "off"],
                    help="capture the engine-path training step in a hipGraph when eligible")
     p.add_argument("--native_pipeline", default="auto", choices=["auto", "on", "off"],
