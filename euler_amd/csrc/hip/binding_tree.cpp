@@ -620,7 +620,13 @@ class TreePlan : private PlanDict {
     }
     a.labels = lab.data_ptr();
     a.label_mode = mode;
-    a.inv_scale = 1.f / static_cast<float>(B_ * C_real_);
+    // "loss": 0 = per-column sigmoid cross-entropy (default), 1 = row softmax cross-entropy
+    const int loss = has("loss") ? static_cast<int>(geti("loss")) : kTrLossSigmoid;
+    TORCH_CHECK(loss == kTrLossSigmoid || loss == kTrLossSoftmax, "TreePlan: loss must be 0 (sigmoid) or 1 (softmax)");
+    TORCH_CHECK(loss != kTrLossSoftmax || C_ <= kTrSoftmaxMaxC, "TreePlan: the softmax head holds one 16-column ",
+                "logits tile per wave of its block: at most ", kTrSoftmaxMaxC, " (padded) classes, got ", C_);
+    a.loss = loss;
+    a.inv_scale = loss == kTrLossSoftmax ? 1.f / static_cast<float>(B_) : 1.f / static_cast<float>(B_ * C_real_);
     a.A_kt = bf("A" + std::to_string(last) + "_kt", B_ * Hin2);
     a.h_kt = bf("h_kt", B_ * H);
     a.emb_kt = bf("emb_kt", (int64_t)B_ * E_);
@@ -633,7 +639,8 @@ class TreePlan : private PlanDict {
     a.head_part = zeros_ptr<float>(nblk * 4, torch::kFloat32);
     a.prof = nullptr;
     const size_t lds = eh_tr_head_lds(a.Hin2, a.H, a.E, a.C, mode);
-    TORCH_CHECK(lds <= 160 * 1024 - 64, "TreePlan: head tile does not fit in LDS (", lds, " bytes)");
+    TORCH_CHECK(lds + (loss == kTrLossSoftmax ? eh_tr_head_softmax_lds() : 0) <= 160 * 1024 - 64,
+                "TreePlan: head tile does not fit in LDS (", lds, " bytes)");
     if (L_ == 3) {
       TrBwdArgs& b = bwd1_;
       b.dA = f32("dA2", B_ * 2 * dims_[1]);

@@ -113,7 +113,14 @@ struct TrFwdArgs {
                          // forward (mode 3)
 };
 
-// head: last SAGE conv + fc + out_fc + sigmoid-CE + backward down to dA, kTrHeadRows roots / block
+// loss of the head (TrHeadArgs::loss; plan key "loss"): per-column sigmoid cross-entropy with
+// micro-F1 counts (multi-label, the reference's), or row softmax cross-entropy with accuracy
+// counts (single-label).  The softmax head keeps one logits tile per wave across its row
+// merge, which bounds the padded label width.
+constexpr int kTrLossSigmoid = 0, kTrLossSoftmax = 1;
+constexpr int kTrSoftmaxMaxC = 256;  // 16 waves x 16 columns
+
+// head: last SAGE conv + fc + out_fc + loss + backward down to dA, kTrHeadRows roots / block
 struct TrHeadArgs {
   const uint16_t* A;     // [B][Hin2] bf16 rows [self | mean]
   int32_t Hin2, H, E, C, C_real;
@@ -124,14 +131,17 @@ struct TrHeadArgs {
   const int32_t* roots;  // [B] (the forward's copy of the batch's roots)
   const void* labels;    // mode 0: int16 [N] class ids, 1: int32 [N], 2: bf16 [N][C] dense
   int32_t label_mode;
-  float inv_scale;       // 1 / (B * C_real)
+  float inv_scale;       // sigmoid: 1 / (B * C_real); softmax: 1 / B
   uint16_t *A_kt, *h_kt, *emb_kt, *dlog_kt, *demb_kt, *g_kt;
   float* dA;             // [B][Hin2] fp32 (nullptr: no lower layer)
   float* dbfc_part;      // [B/kTrHeadRows][E] per-block fc-bias gradient (reduced by tr_opt)
-  float* head_part;      // [B/kTrHeadRows][4] per-block loss, tp, fp, fn (reduced by tr_opt)
+  float* head_part;      // [B/kTrHeadRows][4] per-block loss, tp, fp, fn (reduced by tr_opt);
+                         // softmax: loss, correct rows, wrong rows, wrong rows (so the F1 of
+                         // the three counts is the accuracy)
   long long* prof;       // optional per-block phase stamps [B/16][8]
   TrSampleArgs smp;      // the next step's sampler, run by extra blocks of the launch on the
   int32_t nsample;       // CUs the head leaves idle (0: none)
+  int32_t loss;          // kTrLossSigmoid / kTrLossSoftmax: which kernel eh_tr_head launches
 };
 
 // pair head (unsupervised GraphSAGE, models/sage_tower.py): for kTrHeadRows sources per
@@ -304,6 +314,7 @@ hipError_t eh_tr_opt(const euler_hip::TrOptArgs* a, int mode, hipStream_t s);
 size_t eh_tr_fwd_lds(int D, int H, int bm, int FL, int mode);
 size_t eh_tr_fwd2_lds(int D, int FL);
 size_t eh_tr_head_lds(int Hin2, int H, int E, int C, int label_mode);
+size_t eh_tr_head_softmax_lds();  // static LDS of the softmax head on top of eh_tr_head_lds
 size_t eh_tr_pair_head_lds(int K, int H0x2, int H1, int E);
 hipError_t eh_tr_pair_head(const euler_hip::TrPairHeadArgs* a, hipStream_t s);
 }

@@ -1,5 +1,5 @@
 // The head launches of the fused GraphSAGE tree step (overview: tree_fwd.hip): tr_head_kernel
-// (last conv + fc + out_fc + sigmoid CE + backward to dA, and the next step's sampler on the
+// (last conv + fc + out_fc + sigmoid or softmax CE + backward to dA, and the next step's sampler on the
 // CUs it leaves idle) and tr_pair_head_kernel (the two towers of the unsupervised model), with
 // the 16-row MFMA GEMM out of LDS that both are made of.
 #include <algorithm>
@@ -87,6 +87,49 @@ __device__ __forceinline__ int tr_head_ld(int w) { return w + 16; }  // see sw_o
 // fc and out_fc enter the critical path only through Wc = Wout Wfc (TrCombArgs): the
 // reference model has no nonlinearity between them, so logits and their gradient to h are
 // the same products with two dependent GEMM phases fewer.
+//
+// LOSS == kTrLossSoftmax (tr_head_kernel<1>) splits the logits epilogue of P1 in two around
+// one more barrier, since a row's statistics span the C / 16 <= 16 waves that hold its tiles:
+//   P1a each logits wave keeps x = logits + bc of its tile in registers and reduces it over the
+//       16 column lanes to per-row (max, sum exp(x - max), arg-max column; dense labels: label
+//       sum, label arg-max) -> sm_s[row][tile]; padded columns enter none of them
+//   P1b every logits wave merges the tiles of its rows in tile order (fixed order, no atomics:
+//       the same bits in every launch) and finishes its own tile: p = exp(x - m) / Z,
+//       d = bf16((s p - y) / B), row loss = sum_c y_c (m + log Z - x_c); wave 0 counts the rows
+//       whose arg-max (ties: lowest column) is the label's: tp = correct, fp = fn = wrong
+// The emb waves only pass the barrier.  One logits job per wave: C <= kTrSoftmaxMaxC.
+constexpr int kSmStats = 6;  // per (row, tile): max, sum, arg-max, label sum, label max, label arg-max
+
+// (max, its lowest column) and the sum over the 16 column lanes of a tile row; every lane ends
+// with the same bits (the butterfly adds the same pairs in every lane)
+__device__ __forceinline__ void sm_argmax16(float& m, int& am) {
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oa = __shfl_xor(am, o, 64);
+    if (om > m || (om == m && oa < am)) {
+      m = om;
+      am = oa;
+    }
+  }
+}
+__device__ __forceinline__ float sm_sum16(float v) {
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// the softmax head's [HB][HNW][kSmStats] row statistics; no LDS in the sigmoid instantiation
+template <int LOSS>
+__device__ __forceinline__ float* sm_stats() {
+  if constexpr (LOSS == kTrLossSoftmax) {
+    __shared__ float sm_s[HB * HNW * kSmStats];
+    return sm_s;
+  } else {
+    return nullptr;
+  }
+}
+
+template <int LOSS>
 __global__ __launch_bounds__(HNW * 64) void tr_head_kernel(TrHeadArgs a) {
   extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
   const int nhb = static_cast<int>(gridDim.x) - a.nsample;
@@ -189,6 +232,8 @@ __global__ __launch_bounds__(HNW * 64) void tr_head_kernel(TrHeadArgs a) {
   // P1: logits (+ loss, dlogits, F1 counts; padded label columns excluded) and emb
   float lsum = 0.f;
   int tp = 0, fp = 0, fn = 0;
+  float sx[4], sy[4];  // softmax: the wave's logits tile and its label tile across the row merge
+  float* const sm_s = sm_stats<LOSS>();
   for (int j = wave; j < n1; j += HNW) {
     const bf16_t* Bf;
     int cc;
@@ -200,26 +245,57 @@ __global__ __launch_bounds__(HNW * 64) void tr_head_kernel(TrHeadArgs a) {
     if (j < nl) {
       const bool valid = col < a.C_real;
       const float bias = a.bc[col];
-#pragma unroll
-      for (int m = 0; m < HFM; ++m) {
-        float d[4];
+      if constexpr (LOSS == kTrLossSoftmax) {  // P1a (j == wave: n1 <= HNW)
+        static_assert(HFM == 1, "the softmax head keeps one 16-row tile per wave");
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-          const int row = m * 16 + lg * 4 + jj;
-          const float xv = acc[m][0][jj] + bias;
-          const float y = a.label_mode < 2 ? ((lab_s[row] == col) ? 1.f : 0.f) : bf2f(Ly[row * C + col]);
-          const float p = 1.f / (1.f + __expf(-xv));
-          if (valid) {
-            lsum += fmaxf(xv, 0.f) - xv * y + log1pf(__expf(-fabsf(xv)));
-            const bool pred = xv >= 0.f, pos = y > 0.5f;
-            tp += pred && pos;
-            fp += pred && !pos;
-            fn += !pred && pos;
+          const int row = lg * 4 + jj;
+          sx[jj] = acc[0][0][jj] + bias;
+          sy[jj] = a.label_mode < 2 ? ((lab_s[row] == col) ? 1.f : 0.f) : bf2f(Ly[row * C + col]);
+          float mx = valid ? sx[jj] : -INFINITY;
+          int am = col;
+          sm_argmax16(mx, am);
+          const float z = sm_sum16(valid ? __expf(sx[jj] - mx) : 0.f);
+          float* st = sm_s + (row * HNW + j) * kSmStats;
+          if (a.label_mode == 2) {
+            const float ys = sm_sum16(valid ? sy[jj] : 0.f);
+            float ym = valid ? sy[jj] : -INFINITY;
+            int ya = col;
+            sm_argmax16(ym, ya);
+            if (lr == 0) {
+              st[3] = ys;
+              st[4] = ym;
+              st[5] = __int_as_float(ya);
+            }
           }
-          d[jj] = valid ? bf2f(f2bf((p - y) * a.inv_scale)) : 0.f;
-          Dl[sw_off(row, col, ldc)] = f2bf(d[jj]);
+          if (lr == 0) {
+            st[0] = mx;
+            st[1] = z;
+            st[2] = __int_as_float(am);
+          }
         }
-        kt_store4(a.dlog_kt, r0 + m * 16 + lg * 4, col, C, d[0], d[1], d[2], d[3]);
+      } else {
+#pragma unroll
+        for (int m = 0; m < HFM; ++m) {
+          float d[4];
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) {
+            const int row = m * 16 + lg * 4 + jj;
+            const float xv = acc[m][0][jj] + bias;
+            const float y = a.label_mode < 2 ? ((lab_s[row] == col) ? 1.f : 0.f) : bf2f(Ly[row * C + col]);
+            const float p = 1.f / (1.f + __expf(-xv));
+            if (valid) {
+              lsum += fmaxf(xv, 0.f) - xv * y + log1pf(__expf(-fabsf(xv)));
+              const bool pred = xv >= 0.f, pos = y > 0.5f;
+              tp += pred && pos;
+              fp += pred && !pos;
+              fn += !pred && pos;
+            }
+            d[jj] = valid ? bf2f(f2bf((p - y) * a.inv_scale)) : 0.f;
+            Dl[sw_off(row, col, ldc)] = f2bf(d[jj]);
+          }
+          kt_store4(a.dlog_kt, r0 + m * 16 + lg * 4, col, C, d[0], d[1], d[2], d[3]);
+        }
       }
     } else {
       const float b = a.bfc[col];
@@ -233,6 +309,52 @@ __global__ __launch_bounds__(HNW * 64) void tr_head_kernel(TrHeadArgs a) {
       int cn;
       job1(j + HNW, Bn, cn);
       tr_prefetch(Bn, cn, 1 << 30, H, lane, pre);
+    }
+  }
+  if constexpr (LOSS == kTrLossSoftmax) {  // P1b
+    __syncthreads();
+    if (wave < nl) {
+      const int col = wave * 16 + lr, nlr = (a.C_real + 15) >> 4;  // tiles with a real column
+      const bool valid = col < a.C_real;
+      float d[4];
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int row = lg * 4 + jj;
+        const float* st = sm_s + row * HNW * kSmStats;
+        float mx = st[0], ys = 1.f, ym = -INFINITY;
+        int am = __float_as_int(st[2]), lab = 0;
+        for (int t = 1; t < nlr; ++t)
+          if (st[t * kSmStats] > mx) {  // ties stay with the lower tile
+            mx = st[t * kSmStats];
+            am = __float_as_int(st[t * kSmStats + 2]);
+          }
+        float Z = 0.f;
+        for (int t = 0; t < nlr; ++t) Z += st[t * kSmStats + 1] * __expf(st[t * kSmStats] - mx);
+        if (a.label_mode < 2) {
+          lab = lab_s[row];
+        } else {
+          ys = 0.f;
+          for (int t = 0; t < nlr; ++t) {
+            ys += st[t * kSmStats + 3];
+            if (st[t * kSmStats + 4] > ym) {
+              ym = st[t * kSmStats + 4];
+              lab = __float_as_int(st[t * kSmStats + 5]);
+            }
+          }
+        }
+        const float lse = mx + logf(Z);
+        const float p = valid ? __expf(sx[jj] - mx) / Z : 0.f;
+        if (valid) lsum += sy[jj] * (lse - sx[jj]);
+        d[jj] = valid ? bf2f(f2bf((ys * p - sy[jj]) * a.inv_scale)) : 0.f;
+        Dl[sw_off(row, col, ldc)] = f2bf(d[jj]);
+        if (wave == 0 && lr == 0) {
+          const bool ok = am == lab;
+          tp += ok;
+          fp += !ok;
+          fn += !ok;
+        }
+      }
+      kt_store4(a.dlog_kt, r0 + lg * 4, col, C, d[0], d[1], d[2], d[3]);
     }
   }
   {
@@ -327,6 +449,11 @@ __global__ __launch_bounds__(HNW * 64) void tr_head_kernel(TrHeadArgs a) {
   }
   TR_STAMP(a.prof, blk, 5);
 }
+
+// one kernel per loss: tr_head_kernel<kTrLossSigmoid> carries nothing of the softmax epilogue
+// (its code is the untemplated kernel's, instruction for instruction: tools/kernel_isa.py)
+template __global__ void tr_head_kernel<kTrLossSigmoid>(TrHeadArgs);
+template __global__ void tr_head_kernel<kTrLossSoftmax>(TrHeadArgs);
 
 // ----------------------------------------------------------------------------
 // tr_pair_head: the head of the unsupervised GraphSAGE step (see TrPairHeadArgs; reference
@@ -533,6 +660,9 @@ size_t eh_tr_head_lds(int Hin2, int H, int E, int C, int label_mode) {
   return el * sizeof(bf16_t);
 }
 
+// static LDS the softmax head adds to eh_tr_head_lds: its row statistics (sm_stats)
+size_t eh_tr_head_softmax_lds() { return static_cast<size_t>(HB) * HNW * kSmStats * sizeof(float); }
+
 hipError_t eh_tr_head(const TrHeadArgs* a, int64_t B, hipStream_t s) {
   if (!a->A || !a->W || !a->Wfc || !a->WfcT || !a->Wout || !a->WoutT || !a->Wc || !a->WcT || !a->bc || !a->bfc ||
       !a->roots || !a->labels ||
@@ -542,14 +672,24 @@ hipError_t eh_tr_head(const TrHeadArgs* a, int64_t B, hipStream_t s) {
   if (B % 32 != 0 || a->H % 16 != 0 || a->E % 32 != 0 || a->C % 32 != 0 || a->Hin2 % 32 != 0 ||
       a->C_real > a->C || a->C_real <= 0)
     return hipErrorInvalidValue;
+  if (a->label_mode < 0 || a->label_mode > 2 || (a->loss != kTrLossSigmoid && a->loss != kTrLossSoftmax))
+    return hipErrorInvalidValue;
+  const bool softmax = a->loss == kTrLossSoftmax;
+  // softmax: one logits tile per wave (the tile stays in registers across the row merge)
+  if (softmax && a->C > kTrSoftmaxMaxC) return hipErrorInvalidValue;
   const size_t lds = eh_tr_head_lds(a->Hin2, a->H, a->E, a->C, a->label_mode);
-  if (lds > 160 * 1024 - 64) return hipErrorInvalidValue;
-  EULER_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tr_head_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+  if (lds + (softmax ? eh_tr_head_softmax_lds() : 0) > 160 * 1024 - 64) return hipErrorInvalidValue;
+  const void* fn = softmax ? reinterpret_cast<const void*>(tr_head_kernel<kTrLossSoftmax>)
+                           : reinterpret_cast<const void*>(tr_head_kernel<kTrLossSigmoid>);
+  EULER_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
   // the sampler refills its own roots array, not the one this launch reads
   if (a->nsample > 0 && (!tr_sample_ok(a->smp, kTrHeadSampleRows, a->nsample) || a->smp.roots == a->roots))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(tr_head_kernel, dim3(static_cast<uint32_t>(B / HB + a->nsample)), dim3(HNW * 64), lds, s, *a);
+  const dim3 grid(static_cast<uint32_t>(B / HB + a->nsample));
+  if (softmax)
+    hipLaunchKernelGGL(tr_head_kernel<kTrLossSoftmax>, grid, dim3(HNW * 64), lds, s, *a);
+  else
+    hipLaunchKernelGGL(tr_head_kernel<kTrLossSigmoid>, grid, dim3(HNW * 64), lds, s, *a);
   return hipGetLastError();
 }
 

@@ -922,6 +922,7 @@ class BaseEstimator:
         if met is not None and hasattr(met, "reset"):
             met.reset()
         name = getattr(self.model, "metric_name", getattr(tr, "metric_name", "f1"))
+        softmax = getattr(self.model, "loss", "sigmoid") == "softmax"
         losses, res, steps, n, t0 = [], {}, 0, 0, time.time()
         extract = lambda b: self.get_evaluate_from_input(b, self.params)  # noqa: E731
         infer_logits = self._infer_fn(tr, "logits")
@@ -933,8 +934,13 @@ class BaseEstimator:
                 _, logits, y = infer_logits(src, **kw)
             except NotImplementedError:
                 return None
-            losses.append(float(F.binary_cross_entropy_with_logits(logits, y.float())))
-            value = met(y.detach(), torch.sigmoid(logits).detach()) if met is not None else float("nan")
+            if softmax:  # the model's loss kind (SuperviseModel.forward): class id = label arg-max
+                cls = y.argmax(1)
+                losses.append(float(F.cross_entropy(logits.float(), cls)))
+                value = met(cls.detach(), logits.detach().argmax(1)) if met is not None else float("nan")
+            else:
+                losses.append(float(F.binary_cross_entropy_with_logits(logits, y.float())))
+                value = met(y.detach(), torch.sigmoid(logits).detach()) if met is not None else float("nan")
             res = {"loss": float(np.mean(losses)), name: float(value)}
             steps += 1
             n += int(torch.as_tensor(src).numel())

@@ -159,6 +159,13 @@ def materialize_without_engine(model):
                          "that only a first engine batch can materialise")
 
 
+def _check_loss(model, tr):
+    """never train a ``loss="softmax"`` model with a trainer whose head is the sigmoid one"""
+    if getattr(model, "loss", "sigmoid") == "softmax" and not getattr(tr, "trains_softmax", False):
+        raise ValueError(f"{type(tr).__name__} has no softmax loss: loss='softmax' trains on the device path "
+                         "through SageTrainer (SupervisedGraphSage) or the generic flow trainers")
+
+
 def build_device_trainer(est, model, first):
     """the first registered trainer that accepts ``model`` (NoDeviceTrainer if none does).
     A model with a historical-embedding encoder is only taken by a store-aware trainer:
@@ -176,6 +183,7 @@ def build_device_trainer(est, model, first):
             # autograd gradient sync: every device trainer runs its own update and sync
             est._prepare(first, build_optimizer=False)
             tr = builder(Ctx(est, model))
+            _check_loss(model, tr)
             tr.device_trainer_kind = name
             return tr
     if stores:

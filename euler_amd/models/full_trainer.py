@@ -63,7 +63,12 @@ def infer_flow(owner, graph, masks, self_loops, n):
 
 
 class FullFlowTrainer(CapturedTrainer):
-    metric_name = "f1"
+    trains_softmax = True  # estimator/device_trainers.py _check_loss
+    @property
+    def metric_name(self):
+        """"f1", or "acc" for a ``loss="softmax"`` model (row accuracy in the same three counts)"""
+        return "acc" if self._softmax() else "f1"
+
     # False: a subclass builds its node inputs itself (models/node_inputs.py: id / sparse-feature
     # embeddings, possibly no dense column at all)
     needs_dense_features = True
@@ -173,12 +178,30 @@ class FullFlowTrainer(CapturedTrainer):
     def infer_embed(self, ids):
         return self.infer_logits(ids)[0]
 
+    def _softmax(self) -> bool:
+        return getattr(getattr(self, "model", None), "loss", "sigmoid") == "softmax"
+
+    def _head_loss(self, logits, labels, rows):
+        """the model's loss of ``logits`` against ``labels[rows]``, its counts added to
+        :attr:`counts` in place (a captured step keeps accumulating)"""
+        if not self._softmax():
+            # sigmoid cross-entropy + the F1 counts in one kernel pair (gnn_ops.bce_f1_loss)
+            return gnn_ops.bce_f1_loss(logits, labels, rows, self.counts)
+        # single-label: cross-entropy against the class id (the label row's arg-max); correct /
+        # wrong / wrong rows in the tp / fp / fn slots make the F1 of the counts the accuracy
+        cls = labels[rows].argmax(1)
+        loss = F.cross_entropy(logits, cls)
+        with torch.no_grad():
+            ok = (logits.argmax(1) == cls).sum()
+            wrong = cls.numel() - ok
+            self.counts += torch.stack([ok, wrong, wrong])
+        return loss
+
     def _forward_loss(self):
         self._draw()
         roots = self.graph.sample_node(self.B, stream_id=1).long()
         logits, df = self._forward(roots)
-        # sigmoid cross-entropy + the F1 counts in one kernel pair (gnn_ops.bce_f1_loss)
-        loss = gnn_ops.bce_f1_loss(logits, self.labels, roots, self.counts)
+        loss = self._head_loss(logits, self.labels, roots)
         self._samples = roots
         return loss
 
@@ -212,7 +235,8 @@ class FullFlowTrainer(CapturedTrainer):
         logits = self.model.embed(raw)
         logits = self.model.out_fc(logits).float()
         y = ge.get_dense_feature(raw, [self.model.label_idx], [self.model.label_dim])[0].to(logits.device).float()
-        loss = F.binary_cross_entropy_with_logits(logits, y)
+        loss = F.cross_entropy(logits, y.argmax(1)) if self._softmax() else \
+            F.binary_cross_entropy_with_logits(logits, y)
         loss.backward()
         grads = {n: p.grad.detach().clone() for n, p in params.items()}
         for n, p in params.items():
@@ -272,7 +296,7 @@ class ShardedFlowTrainer(FullFlowTrainer):
         roots = self.graph.sample_node(self.B, stream_id=1).long()
         logits, df = self._forward(roots)
         y = self.graph.gather_labels(roots).float().contiguous()
-        loss = gnn_ops.bce_f1_loss(logits, y, self._rows, self.counts)
+        loss = self._head_loss(logits, y, self._rows)
         self._samples = roots
         return loss
 

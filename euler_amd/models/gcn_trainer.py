@@ -154,8 +154,13 @@ class GcnTrainer(CapturedTrainer):
     @staticmethod
     def supports(model, graph=None, batch_size=None) -> bool:
         """SupervisedGCN-shaped: 1-2 bias-free GCNConvs on GCNDataFlow with self loops, fc with
-        bias, out_fc without; conv widths <= 64, inputs <= 128, fc / label widths <= 128"""
+        bias, out_fc without; conv widths <= 64, inputs <= 128, fc / label widths <= 128.
+        Sigmoid models only: the fused GCN head (csrc/hip/gcn.hip, and graph_cls.hip of the
+        graph classifiers) has no softmax loss, so a ``loss="softmax"`` model trains on the
+        generic :class:`FullFlowTrainer`."""
         if os.environ.get("EULER_AMD_GCN_FUSED", "1") == "0":
+            return False
+        if getattr(model, "loss", "sigmoid") != "sigmoid":
             return False
         convs = _gcn_shape(model)
         if convs is None:

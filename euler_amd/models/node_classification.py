@@ -59,8 +59,8 @@ class SupervisedGNN(SuperviseModel):
     """Generic ``conv + flow`` supervised model."""
 
     def __init__(self, conv, flow, dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                 max_id=-1, metric_name="f1", conv_kwargs=None, add_self_loops=False):
-        super().__init__(label_idx, label_dim, metric_name)
+                 max_id=-1, metric_name="f1", conv_kwargs=None, add_self_loops=False, loss="sigmoid"):
+        super().__init__(label_idx, label_dim, metric_name, loss=loss)
         self.gnn = FeatureGNN(conv, flow, dims, fanouts, metapath, feature_idx, feature_dim,
                               add_self_loops=add_self_loops, max_id=max_id, conv_kwargs=conv_kwargs)
 
@@ -73,74 +73,79 @@ class SupervisedGNN(SuperviseModel):
 
 class SupervisedGraphSage(SupervisedGNN):
     def __init__(self, dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim, max_id=-1,
-                 metric_name="f1"):
+                 metric_name="f1", loss="sigmoid"):
         super().__init__("sage", "sage", dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         max_id, metric_name)
+                         max_id, metric_name, loss=loss)
 
 
 class SupervisedGCN(SupervisedGNN):
-    def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, metric_name="f1"):
+    def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, metric_name="f1",
+                 loss="sigmoid"):
         super().__init__("gcn", "full", dims, None, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name)
+                         metric_name=metric_name, loss=loss)
 
 
 class GAT(SupervisedGNN):
     def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, head_num=1, concat=True,
-                 improved=False, metric_name="f1"):
+                 improved=False, metric_name="f1", loss="sigmoid"):
         super().__init__(C.MultiHeadGATConv, "full", dims, None, metapath, feature_idx, feature_dim, label_idx,
                          label_dim, metric_name=metric_name,
-                         conv_kwargs={"heads": head_num, "concat": concat, "improved": improved})
+                         conv_kwargs={"heads": head_num, "concat": concat, "improved": improved}, loss=loss)
 
 
 class FastGCN(SupervisedGNN):
-    def __init__(self, dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim, metric_name="f1"):
+    def __init__(self, dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim, metric_name="f1",
+                 loss="sigmoid"):
         super().__init__("gcn", "fast", dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name)
+                         metric_name=metric_name, loss=loss)
 
 
 class AdaptiveGCN(SupervisedGNN):
-    def __init__(self, dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim, metric_name="f1"):
+    def __init__(self, dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim, metric_name="f1",
+                 loss="sigmoid"):
         super().__init__("gcn", "adapt", dims, fanouts, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name)
+                         metric_name=metric_name, loss=loss)
 
 
 class AGNN(SupervisedGNN):
-    def __init__(self, metric, dims, metapath, feature_idx, feature_dim, label_idx, label_dim):
+    def __init__(self, metric, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, loss="sigmoid"):
         super().__init__("agnn", "full", dims, None, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric)
+                         metric_name=metric, loss=loss)
 
 
 class APPNP(SupervisedGNN):
     def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, K=10, alpha=0.1,
-                 metric_name="f1"):
+                 metric_name="f1", loss="sigmoid"):
         super().__init__("appnp", "full", dims, None, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name, conv_kwargs={"K": K, "alpha": alpha})
+                         metric_name=metric_name, conv_kwargs={"K": K, "alpha": alpha}, loss=loss)
 
 
 class ARMA(SupervisedGNN):
     def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, K=1, num_layers=1,
-                 metric_name="f1"):
+                 metric_name="f1", loss="sigmoid"):
         super().__init__("arma", "full", dims, None, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name, conv_kwargs={"K": K, "num_layers": num_layers})
+                         metric_name=metric_name, conv_kwargs={"K": K, "num_layers": num_layers}, loss=loss)
 
 
 class DNA(SupervisedGNN):
     def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, head_num=1, group_num=1,
-                 metric_name="f1"):
+                 metric_name="f1", loss="sigmoid"):
         super().__init__("dna", "full", dims, None, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name, conv_kwargs={"heads": head_num, "groups": group_num})
+                         metric_name=metric_name, conv_kwargs={"heads": head_num, "groups": group_num}, loss=loss)
 
 
 class SGCN(SupervisedGNN):
-    def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, K=1, metric_name="f1"):
+    def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, K=1, metric_name="f1",
+                 loss="sigmoid"):
         super().__init__("sgcn", "full", dims, None, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name, conv_kwargs={"K": K})
+                         metric_name=metric_name, conv_kwargs={"K": K}, loss=loss)
 
 
 class TAGCN(SupervisedGNN):
-    def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, K=3, metric_name="f1"):
+    def __init__(self, dims, metapath, feature_idx, feature_dim, label_idx, label_dim, K=3, metric_name="f1",
+                 loss="sigmoid"):
         super().__init__("tag", "full", dims, None, metapath, feature_idx, feature_dim, label_idx, label_dim,
-                         metric_name=metric_name, conv_kwargs={"K": K})
+                         metric_name=metric_name, conv_kwargs={"K": K}, loss=loss)
 
 
 class GeniePath(SuperviseModel):

@@ -11,13 +11,20 @@ previous hops), trained with adam / adagrad / sgd / momentum (``utils/optimizers
 
 Execution (MI355X): the graph (CSR + prefix-sum weights), the feature table and the
 labels live in HBM (:meth:`DeviceGraph.from_engine` uploads a loaded dataset;
-:meth:`DeviceGraph.synthetic` builds one on the GPU).  A training step is 4 gfx950
-launches for 2 hops (``csrc/hip/tree_fwd.hip``, ``tree_head.hip``, ``tree_dw.hip``): sampling + gather + GEMM + tree mean,
-the fused head (last conv, fc, out_fc, loss, backward), the grouped split-K dW with the
-tree routing of the outer layer's gradient built in, and the reduce + optimizer + bf16
-weight shadows.  All state (RNG counter, optimizer step) is on the device, so the step
+:meth:`DeviceGraph.synthetic` builds one on the GPU).  A training step is 3 gfx950
+launches for 2 hops (``csrc/hip/tree_fwd.hip``, ``tree_head.hip``, ``tree_dw.hip``):
+sampling + gather + GEMM + tree mean, the fused head (last conv, fc, out_fc, loss, backward),
+and the grouped split-K dW with the tree routing of the outer layer's gradient built in, whose
+fold and trailing blocks run the reduce + optimizer + bf16 weight shadows (a fourth launch of
+their own under data parallelism).  All state (RNG counter, optimizer step) is on the device, so the step
 is captured once into a hipGraph and replayed; with data parallelism the flat gradient
 is all-reduced (RCCL) between the split-K reduce and the optimizer.
+
+``loss="softmax"`` (single-label data: exclusive classes) replaces the per-column sigmoid
+cross-entropy and micro-F1 by the row softmax cross-entropy and accuracy, in the head's own
+softmax instantiation (``tree_head.hip``, at most 256 padded classes) and in the CPU twin and
+oracles below; the class-id label tables (int16 / int32) and dense rows (a target
+distribution up to its sum) are read as before, and every launch after the head is unchanged.
 
 Layout: dims are padded (features to 16, conv widths to 64, fc / labels to 32) with
 zero rows / columns that provably stay zero (their gradients are exactly zero), and the
@@ -50,6 +57,38 @@ from euler_amd.models.captured import new_graph
 __all__ = ["SageTrainer", "sage_param_names"]
 
 _OPT_KIND = {"adam": 0, "adagrad": 1, "sgd": 2, "momentum": 3}
+# plan key "loss" (csrc/hip/tree_args.h kTrLossSigmoid / kTrLossSoftmax)
+_LOSS_KIND = {"sigmoid": 0, "softmax": 1}
+_SOFTMAX_MAX_CP = 256  # kTrSoftmaxMaxC: one 16-column logits tile per wave of the head's block
+
+
+def loss_kind(loss):
+    """validated loss name: "sigmoid" (per-column binary cross-entropy, micro-F1) or "softmax"
+    (row cross-entropy over exclusive classes, accuracy)"""
+    if loss not in _LOSS_KIND:
+        raise ValueError(f"loss must be one of {sorted(_LOSS_KIND)}, got {loss!r}")
+    return loss
+
+
+def head_loss(logits, y, loss="sigmoid"):
+    """mean loss of a batch of logits against dense label rows ``y``.  softmax: the rows of
+    ``y`` are target distributions up to their sum s, row loss = s logsumexp(x) - sum_c y_c x_c
+    (``F.cross_entropy`` against the class id when a row is one-hot), mean over the rows."""
+    if loss == "softmax":
+        return (y.sum(1) * torch.logsumexp(logits, 1) - (y * logits).sum(1)).mean()
+    return F.binary_cross_entropy_with_logits(logits, y)
+
+
+def head_counts(logits, y, loss="sigmoid"):
+    """(tp, fp, fn) of a batch.  sigmoid: micro-F1 counts at threshold 0.5.  softmax: (correct
+    rows, wrong, wrong) by arg-max (ties: lowest column), so the F1 of the counts is the accuracy."""
+    if loss == "softmax":
+        # first maximum: torch.argmax does not promise which of equal maxima it returns
+        first = lambda t: (t == t.max(1, keepdim=True).values).int().argmax(1)  # noqa: E731
+        ok = int((first(logits) == first(y)).sum())
+        return ok, logits.shape[0] - ok, logits.shape[0] - ok
+    pred, pos = logits >= 0, y > 0.5
+    return int((pred & pos).sum()), int((pred & ~pos).sum()), int((~pred & pos).sum())
 
 
 def _ceil(x: int, m: int) -> int:
@@ -86,11 +125,17 @@ _PIPELINE = os.environ.get("EULER_AMD_PIPELINE", "0") == "1"
 
 
 class SageTrainer:
+    trains_softmax = True  # estimator/device_trainers.py _check_loss
+
     def __init__(self, graph, batch_size, fanouts, dims, label_dim, features=None, labels=None, metapath=None,
                  add_self_loops=False, optimizer="adam", learning_rate=0.01, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, init=None, init_seed=0, keep_samples=True, grad_buckets=1, feature_shard=None,
-                 feature_dim=None):
+                 feature_dim=None, loss="sigmoid"):
         self.graph = graph
+        # "sigmoid": per-column binary cross-entropy + micro-F1 (multi-label, the reference's);
+        # "softmax": row cross-entropy + accuracy (single-label: exclusive classes)
+        self.loss_name = loss_kind(loss)
+        self.metric_name = "acc" if loss == "softmax" else "f1"
         # row-sharded features (graph/sharded_features.py): this rank holds rows r % W; each
         # step's sampled rows come over the all-to-all into a fixed cache the forward reads
         self.fshard = feature_shard
@@ -139,6 +184,9 @@ class SageTrainer:
         self.Dp = _ceil(self.D, 16)
         self.Hp = [_ceil(h, 64) for h in self.conv_dims]
         self.Ep, self.Cp = _ceil(self.E, 32), _ceil(self.C, 32)
+        if self.loss_name == "softmax" and graph.device.type == "cuda" and self.Cp > _SOFTMAX_MAX_CP:
+            raise ValueError(f"the softmax head takes at most {_SOFTMAX_MAX_CP} classes (label_dim {self.C}): every "
+                             "wave of its block holds one 16-column logits tile across the row merge")
         self.logP = [0] + [_slot(self.fanouts[k - 1]) for k in range(1, self.L)]
         self.M = [self.B]
         for k in range(1, self.L):
@@ -187,6 +235,7 @@ class SageTrainer:
         for m in gnn.sampler.metapath:
             ids = None if m is None else [int(t) for t in np.asarray(ge.get_edge_type_id(m)).reshape(-1)]
             metapath.append(None if ids is None or any(t < 0 for t in ids) else ids)  # -1 = every type
+        kw.setdefault("loss", getattr(model, "loss", "sigmoid"))
         return cls(graph, batch_size, gnn.sampler.fanouts, dims, model.label_dim, metapath=metapath,
                    add_self_loops=bool(getattr(gnn.sampler, "add_self_loops", False)), optimizer=optimizer,
                    learning_rate=learning_rate, init=model, **kw)
@@ -318,7 +367,7 @@ class SageTrainer:
              "E": self.Ep, "C": self.Cp, "C_real": self.C, "include_self": int(self.include_self),
              "indptr": g.indptr, "nbr": g.nbr, "cumw": g.cumw, "num_types": g.num_types, "node_prob": g.node_prob,
              "node_alias": g.node_alias, "root_rows": g.root_rows, "rng": g.rng,
-             "labels": self.labels, "label_mode": self.label_mode,
+             "labels": self.labels, "label_mode": self.label_mode, "loss": _LOSS_KIND[self.loss_name],
              "step": self._step, "flat": self.flat, "grad": self.grad, "m": self.m, "v": self.v,
              "label_rows": getattr(self, "_label_rows", None),
              "offsets": self.offsets, "loss_acc": self.loss_acc, "loss_out": self.loss_out, "counts": self.counts,
@@ -697,7 +746,8 @@ class SageTrainer:
 
     def metric(self) -> float:
         """streaming micro-F1 (threshold 0.5) since the last :meth:`reset_metric`
-        (reference metrics.f1_score)"""
+        (reference metrics.f1_score); under ``loss="softmax"`` the row accuracy (the counts
+        are correct / wrong / wrong rows, of which this formula is correct / rows)"""
         self._check_fuse()
         tp, fp, fn = (self.counts.tolist() if self.on_gpu else self._cpu_counts)
         return 2.0 * tp / max(2.0 * tp + fp + fn, 1e-12)
@@ -886,7 +936,7 @@ class SageTrainer:
         roots, nodes, leaf = samples if samples is not None else self.samples()
         logits = self.logical_forward(params, roots, nodes, leaf)
         y = self._labels_of(roots).to(logits.device)
-        loss = F.binary_cross_entropy_with_logits(logits, y)
+        loss = head_loss(logits, y, self.loss_name)
         loss.backward()
         return float(loss), {k: v.grad.detach() for k, v in params.items()}
 
@@ -903,6 +953,9 @@ class SageTrainer:
         * head: logits = h @ Wc^T + bc (fp32), loss = mean BCE (fp32),
           d = bf((sigmoid - y) / (B C)), emb = bf(h @ Wfc_bf^T + bfc), demb = d @ Wout_bf,
           g = bf(relu'(h) * (d @ Wc)), dA = g @ W_bf (fp32);
+          ``loss="softmax"``: loss = mean_rows(s logsumexp(logits) - sum_c y_c logits_c) and
+          d = bf((s softmax(logits) - y) / B) in fp32, s = sum_c y_c (1 for class ids); the rest
+          is unchanged;
         * routed gradients (tr_dw_route / tr_bwd): g_k-1 = bf(relu'(h_k-1) * route(dA_k)),
           neighbour slots dA[:, H:] * inv_grp, the self slot dA[:, :H] (+ that share with
           self loops);
@@ -949,8 +1002,11 @@ class SageTrainer:
         hl = h[-1]
         logits = hl @ Wc.t() + P["out_fc.weight"] @ bfc
         y = self._labels_of(roots).to(dev)
-        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, y)
-        d = bf((torch.sigmoid(logits) - y) / float(y.numel()))
+        loss = head_loss(logits, y, self.loss_name)
+        if self.loss_name == "softmax":
+            d = bf((y.sum(1, keepdim=True) * torch.softmax(logits, 1) - y) / float(y.shape[0]))
+        else:
+            d = bf((torch.sigmoid(logits) - y) / float(y.numel()))
         emb = bf(hl @ Wfc.t() + bfc)
         demb = d @ Wout
         grads = {"out_fc.weight": d.t() @ emb, "gnn.fc.weight": bf(demb).t() @ hl, "gnn.fc.bias": demb.sum(0)}
@@ -993,13 +1049,11 @@ class SageTrainer:
             table = self.fshard.cache
         logits = self.logical_forward(P, roots, nodes, leaf, table)
         y = self._labels_of(roots).to(logits.device)
-        loss = F.binary_cross_entropy_with_logits(logits, y)
+        loss = head_loss(logits, y, self.loss_name)
         loss.backward()
         with torch.no_grad():
-            pred, pos = logits >= 0, y > 0.5
-            self._cpu_counts[0] += int((pred & pos).sum())
-            self._cpu_counts[1] += int((pred & ~pos).sum())
-            self._cpu_counts[2] += int((~pred & pos).sum())
+            for i, c in enumerate(head_counts(logits, y, self.loss_name)):
+                self._cpu_counts[i] += c
         self.graph.rng[1] += 1
         return loss.detach()
 

@@ -24,9 +24,8 @@ ranks in lockstep (:meth:`ShardedSageTrainer.infer_logits`; the engine of an
 from __future__ import annotations
 
 import torch
-import torch.nn.functional as F
 
-from euler_amd.models.sage_trainer import SageTrainer
+from euler_amd.models.sage_trainer import SageTrainer, head_counts, head_loss
 
 __all__ = ["ShardedSageTrainer"]
 
@@ -227,12 +226,10 @@ class ShardedSageTrainer(SageTrainer):
             yy.scatter_(1, y.long().view(-1, 1), 1.0)
             y = yy
         y = y.float().to(logits.device)
-        loss = F.binary_cross_entropy_with_logits(logits, y)
+        loss = head_loss(logits, y, self.loss_name)
         loss.backward()
         with torch.no_grad():
-            pred, pos_ = logits >= 0, y > 0.5
-            self._cpu_counts[0] += int((pred & pos_).sum())
-            self._cpu_counts[1] += int((pred & ~pos_).sum())
-            self._cpu_counts[2] += int((~pred & pos_).sum())
+            for i, c in enumerate(head_counts(logits, y, self.loss_name)):
+                self._cpu_counts[i] += c
         self.graph.rng[1] += 1
         return loss.detach()

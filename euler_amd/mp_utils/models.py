@@ -270,10 +270,19 @@ class SharedGNNNet(SharedGroupGNNNet):
 
 # ----------------------------------------------------------------------------- model heads
 class SuperviseModel(nn.Module):
-    """label from a dense feature, sigmoid CE, streaming metric (reference mp_utils/base.py:24-47)."""
+    """label from a dense feature, sigmoid CE, streaming metric (reference mp_utils/base.py:24-47).
 
-    def __init__(self, label_idx, label_dim, metric_name="f1"):
+    ``loss="softmax"`` (single-label data: exclusive classes): ``F.cross_entropy`` against the
+    class id, which is the arg-max of the dense label row, and a row-wise metric on
+    (label arg-max, logit arg-max) — accuracy: the default ``"f1"`` becomes ``"acc"``."""
+
+    def __init__(self, label_idx, label_dim, metric_name="f1", loss="sigmoid"):
         super().__init__()
+        if loss not in ("sigmoid", "softmax"):
+            raise ValueError(f"loss must be 'sigmoid' or 'softmax', got {loss!r}")
+        self.loss = loss
+        if loss == "softmax" and metric_name == "f1":
+            metric_name = "acc"
         self.label_idx = label_idx
         self.label_dim = label_dim
         self.metric_name = metric_name
@@ -303,6 +312,11 @@ class SuperviseModel(nn.Module):
             embedding = self.embed(inputs)
         label = label.to(embedding.device)
         logit = self.out_fc(embedding).float()
+        if self.loss == "softmax":
+            cls = label.argmax(1)
+            loss = F.cross_entropy(logit, cls)
+            metric = self.metric(cls.detach(), logit.detach().argmax(1))
+            return embedding, loss, self.metric_name, metric
         loss = F.binary_cross_entropy_with_logits(logit, label.float())
         # streaming metric on the device (no per-step host sync; read at log steps)
         metric = self.metric(label.detach(), torch.sigmoid(logit).detach())

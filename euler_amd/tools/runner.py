@@ -65,6 +65,10 @@ def _mp(a, n=None):
     return [et] * (n or a.layers)
 
 
+# the SupervisedGNN models: they take --loss
+_LOSS_MODELS = ("graphsage", "gcn", "gat", "fastgcn", "adaptivegcn", "agnn", "appnp", "arma", "dna", "sgcn", "tagcn")
+
+
 # name -> (default dataset, estimator kind, builder(args, ds))
 def _models():
     from euler_amd import models as Z
@@ -74,31 +78,35 @@ def _models():
         # reference run_graphsage.py:48: dims = [hidden_dim] * (layers + 1)
         "graphsage": ("cora", "node", lambda a, ds: Z.SupervisedGraphSage(
             _hidden(a, a.hidden_dim), a.fanouts, _mp(a), ds.feature_idx, F(ds), ds.label_idx, ds.label_dim,
-            max_id=ds.max_node_id)),
+            max_id=ds.max_node_id, loss=a.loss)),
         "graphsage_unsup": ("cora", "node", lambda a, ds: Z.UnsupervisedGraphSage(
             _hidden(a, a.dim), a.fanouts, _mp(a), ds.feature_idx, F(ds), _first(ds.train_node_type),
             _first(ds.train_edge_type), ds.max_node_id, num_negs=a.num_negs)),
         "gcn": ("cora", "node", lambda a, ds: Z.SupervisedGCN(_hidden(a, ds.label_dim), _mp(a), ds.feature_idx,
-                                                              F(ds), ds.label_idx, ds.label_dim)),
+                                                              F(ds), ds.label_idx, ds.label_dim, loss=a.loss)),
         "gat": ("cora", "node", lambda a, ds: Z.GAT(_hidden(a, ds.label_dim), _mp(a), ds.feature_idx, F(ds),
-                                                    ds.label_idx, ds.label_dim, head_num=a.head_num)),
+                                                    ds.label_idx, ds.label_dim, head_num=a.head_num,
+                                                    loss=a.loss)),
         "fastgcn": ("cora", "node", lambda a, ds: Z.FastGCN(_hidden(a, ds.label_dim), a.fanouts, _mp(a),
-                                                            ds.feature_idx, F(ds), ds.label_idx, ds.label_dim)),
+                                                            ds.feature_idx, F(ds), ds.label_idx, ds.label_dim,
+                                                            loss=a.loss)),
         "adaptivegcn": ("cora", "node", lambda a, ds: Z.AdaptiveGCN(_hidden(a, ds.label_dim), a.fanouts, _mp(a),
                                                                     ds.feature_idx, F(ds), ds.label_idx,
-                                                                    ds.label_dim)),
+                                                                    ds.label_dim, loss=a.loss)),
         "agnn": ("cora", "node", lambda a, ds: Z.AGNN("f1", _hidden(a, ds.label_dim), _mp(a), ds.feature_idx, F(ds),
-                                                      ds.label_idx, ds.label_dim)),
+                                                      ds.label_idx, ds.label_dim, loss=a.loss)),
         "appnp": ("cora", "node", lambda a, ds: Z.APPNP(_hidden(a, ds.label_dim), _mp(a), ds.feature_idx, F(ds),
-                                                        ds.label_idx, ds.label_dim, K=a.K, alpha=a.alpha)),
+                                                        ds.label_idx, ds.label_dim, K=a.K, alpha=a.alpha,
+                                                        loss=a.loss)),
         "arma": ("cora", "node", lambda a, ds: Z.ARMA(_hidden(a, ds.label_dim), _mp(a), ds.feature_idx, F(ds),
-                                                      ds.label_idx, ds.label_dim, K=a.K)),
+                                                      ds.label_idx, ds.label_dim, K=a.K, loss=a.loss)),
         "dna": ("cora", "node", lambda a, ds: Z.DNA(_hidden(a, ds.label_dim), _mp(a), ds.feature_idx, F(ds),
-                                                    ds.label_idx, ds.label_dim, head_num=a.head_num)),
+                                                    ds.label_idx, ds.label_dim, head_num=a.head_num,
+                                                    loss=a.loss)),
         "sgcn": ("cora", "node", lambda a, ds: Z.SGCN(_hidden(a, ds.label_dim), _mp(a), ds.feature_idx, F(ds),
-                                                      ds.label_idx, ds.label_dim, K=a.K)),
+                                                      ds.label_idx, ds.label_dim, K=a.K, loss=a.loss)),
         "tagcn": ("cora", "node", lambda a, ds: Z.TAGCN(_hidden(a, ds.label_dim), _mp(a), ds.feature_idx, F(ds),
-                                                        ds.label_idx, ds.label_dim, K=a.K)),
+                                                        ds.label_idx, ds.label_dim, K=a.K, loss=a.loss)),
         "geniepath": ("cora", "node", lambda a, ds: Z.GeniePath(a.hidden_dim, _mp(a), ds.label_idx, ds.label_dim,
                                                                 feature_idx=ds.feature_idx, feature_dim=F(ds),
                                                                 head_num=a.head_num, max_id=ds.max_node_id,
@@ -245,6 +253,10 @@ def parse_args(argv=None, model=None):
                         "(layerwise; graphsage: models/sage_infer.py), or the same embeddings computed over "
                         "only the rows the ids reach (frontier: for a few ids of a large graph; a whole-graph "
                         "infer is cheaper with layerwise)")
+    p.add_argument("--loss", default="sigmoid", choices=["sigmoid", "softmax"],
+                   help="supervised GNN models (" + ", ".join(_LOSS_MODELS) + "): per-column sigmoid "
+                        "cross-entropy with micro-F1 (multi-label, the default) or softmax cross-entropy with "
+                        "accuracy (single-label data: exclusive classes)")
     p.add_argument("--cuda_graph", default="auto", choices=["auto", "off"],
                    help="capture the engine-path training step in a hipGraph when eligible")
     p.add_argument("--native_pipeline", default="auto", choices=["auto", "on", "off"],
@@ -274,6 +286,8 @@ def build(a):
     ds_name, kind, builder = MODELS[a.model]
     if (a.use_sparse_feature or a.use_id) and a.model not in ("geniepath", "dgi"):
         raise SystemExit("--use_sparse_feature / --use_id are accepted for geniepath and dgi")
+    if getattr(a, "loss", "sigmoid") != "sigmoid" and a.model not in _LOSS_MODELS:
+        raise SystemExit("--loss softmax is accepted for " + ", ".join(_LOSS_MODELS))
     ds = get_dataset(a.dataset or ds_name, data_dir=a.data_dir, scale=a.scale)
     if getattr(a, "engine_shards", False):
         import torch.distributed as dist
