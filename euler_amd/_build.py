@@ -213,6 +213,14 @@ def build_plan_selftest() -> str:
 # ----------------------------------------------------------------------------
 # HIP kernels (gfx950) + torch binding
 # ----------------------------------------------------------------------------
+# kernels built without the packed fp32 instructions (the two-wide fp32 add / mul / fma forms):
+# their arithmetic compiles to scalar fmac only.  It changes no summation order, only which
+# products are fused; gcn_csr.hip takes 121-123 VGPRs this way against 124-125 with them
+# (profiles/gcn_infer/resource_usage.txt quotes this build line)
+NO_PACKED_FP32 = {"gcn_csr.hip"}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+
+
 def hip_target():
     return os.path.join(ROOT, "_hip_ops" + _EXT_SUFFIX)
 
@@ -250,7 +258,8 @@ def build_hip(max_workers: int = 8) -> str:
     for s in kernels:
         o = os.path.join(objdir, os.path.basename(s) + ".o")
         objs.append(o)
-        jobs.append(([hipcc] + kflags + ["-c", s, "-o", o], o, hdr_m, s))
+        extra = _NO_PACKED_FP32 if os.path.basename(s) in NO_PACKED_FP32 else []
+        jobs.append(([hipcc] + kflags + extra + ["-c", s, "-o", o], o, hdr_m, s))
     for s in bindings:
         o = os.path.join(objdir, os.path.basename(s) + ".o")
         objs.append(o)

@@ -541,6 +541,8 @@ PYBIND11_MODULE(_hip_ops, m) {
   register_graph_build_ops(m);
   auto f = m.def_submodule("frontier");
   register_frontier_ops(f);
+  auto gc = m.def_submodule("gcn_csr");
+  register_gcn_csr_ops(gc);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

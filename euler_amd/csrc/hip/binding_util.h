@@ -46,6 +46,9 @@ void register_graph_build_ops(py::module& m);
 // binding_frontier.cpp: row sets of frontier inference and the layer over a set's compact table
 // (registered on the submodule _hip_ops.frontier)
 void register_frontier_ops(py::module& m);
+// binding_gcn_csr.cpp: full-neighbourhood GCN-family layer over the graph's CSR and its degree
+// counts (registered on the submodule _hip_ops.gcn_csr)
+void register_gcn_csr_ops(py::module& m);
 
 namespace euler_bind {
 

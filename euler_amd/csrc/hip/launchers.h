@@ -254,6 +254,21 @@ hipError_t eh_sage_csr_fwd_mapped(const int64_t* indptr, const int32_t* nbr, con
                                   int Hp, float nbr_scale, float self_scale, int relu, void* out, int out_fp32,
                                   hipStream_t s);
 
+// gcn_csr.hip (full-neighbourhood GCN-family layer over the graph's own CSR:
+// out[m] = cast(c[r] * act(bf16(a[r] * (sum_e b[nbr_e] x[nbr_e] (+ b[r] x[r]))) @ W^T)), r = rows[m] or
+// row_start + m).  x [N, Dp] bf16 / fp32 (Dp % 16 == 0, <= 512), W [Hp, Dp] bf16 row-major
+// (Hp % 64 == 0), tgt_scale a / src_scale b / out_scale c fp32 [N] (b, c may be nullptr: 1), rows
+// [M] int32 or nullptr, out [M, Hp] bf16 / fp32.  A neighbour outside [0, N) adds nothing.
+int eh_gcn_csr_tile_rows();
+hipError_t eh_gcn_csr_fwd(const int64_t* indptr, const int32_t* nbr, int64_t N, int64_t E, int T, uint32_t mask,
+                          const void* x, int x_fp32, int Dp, const float* tgt_scale, const float* src_scale,
+                          const float* out_scale, const int32_t* rows, int64_t row_start, int64_t M, const void* W,
+                          int Hp, int self_loop, int relu, void* out, int out_fp32, hipStream_t s);
+// deg_t [N] = listed masked edges of every row, deg_s [N] (zeroed by the caller) += occurrences
+// of every row in the masked neighbour lists
+hipError_t eh_gcn_csr_degrees(const int64_t* indptr, const int32_t* nbr, int64_t N, int64_t E, int T, uint32_t mask,
+                              int32_t* deg_t, int32_t* deg_s, hipStream_t s);
+
 // frontier.hip (row sets as rank bitmaps: words int32 [eh_frontier_words(N), 2] = (bits, set
 // bits before the word), csr_rowset.h).  N in [1, 2^31)
 int64_t eh_frontier_words(int64_t N);

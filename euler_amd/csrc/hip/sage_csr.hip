@@ -31,8 +31,8 @@
 // row -> table-position step is a template functor, everything else is the same code, so the
 // two give the same bits for the same input rows.  A row the set lacks is never read: it counts
 // as a zero row and is reported through a status word (the only atomic, on the error path).
+#include "hip/csr_dev.h"
 #include "hip/csr_rowset.h"
-#include "hip/tile.h"
 
 namespace euler_hip {
 
@@ -40,7 +40,6 @@ constexpr int kCsrBM = 64;
 constexpr int kCsrThreads = 512;
 constexpr int kCsrWaves = kCsrThreads / 64;
 constexpr int kCsrUnroll = 2;
-constexpr int kCsrMaxD = 512;
 
 struct CsrGraph {
   const int64_t* indptr;  // [N * T + 1]
@@ -50,26 +49,6 @@ struct CsrGraph {
   int T;
   uint32_t mask;
 };
-
-// 8 consecutive features of a row as fp32 (+ the storage bits for a bf16 table)
-__device__ __forceinline__ void csr_load8(const bf16_t* p, float* v) {
-  const uint4_t u = *reinterpret_cast<const uint4_t*>(p);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(u[i] << 16);
-    v[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-  }
-}
-
-__device__ __forceinline__ void csr_load8(const float* p, float* v) {
-  const float4_t a = *reinterpret_cast<const float4_t*>(p);
-  const float4_t b = *reinterpret_cast<const float4_t*>(p + 4);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[i] = a[i];
-    v[4 + i] = b[i];
-  }
-}
 
 // this lane group's share (edges slot, slot + nslots, ...) of row's masked segments:
 // acc[8] += (w_e / tot) * x[nbr_e][8c .. 8c + 7] — the row of the row-normalised adjacency, edge
@@ -237,15 +216,6 @@ __device__ __forceinline__ void csr_gather_tile(const CsrGraph& g, const XT* __r
     __syncthreads();
   }
 }
-
-__device__ __forceinline__ void csr_store4(bf16_t* p, float4_t v) {
-  tl_uint2 o;
-  o[0] = pack_bf16x2(v[0], v[1]);
-  o[1] = pack_bf16x2(v[2], v[3]);
-  *reinterpret_cast<tl_uint2*>(p) = o;
-}
-
-__device__ __forceinline__ void csr_store4(float* p, float4_t v) { *reinterpret_cast<float4_t*>(p) = v; }
 
 // out[row0 .., :] = act(A_lds @ W^T); D = Wfrag x Afrag: lane holds columns 4 (lane >> 4) + j of
 // its 16-column slab for tile row lane & 15

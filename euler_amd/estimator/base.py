@@ -845,7 +845,9 @@ class BaseEstimator:
         if tr is None:
             from euler_amd.estimator.device_trainers import device_infers
 
-            if not device_infers(self.model):
+            # layer-sampled GCNs stay on the engine path except for layer-wise inference, which
+            # treats them as plain GCNs on the device (GcnTrainer.infer_logits_layerwise)
+            if self._infer_mode() != "layerwise" and not device_infers(self.model):
                 return None
             try:
                 tr = self._device_graph_trainer(self._first_batch())
@@ -900,12 +902,13 @@ class BaseEstimator:
         tr = self._device_inference_trainer()
         if tr is None:
             raise ValueError(f"infer_mode={mode!r}: {type(self.model).__name__} has no device inference trainer "
-                             "(layer-wise inference covers SupervisedGraphSage on an unsharded device graph)")
+                             "(layer-wise inference covers SupervisedGraphSage and the fused GCN family on an "
+                             "unsharded device graph)")
         if not callable(getattr(tr, "infer_logits_" + mode, None)) or \
                 not callable(getattr(tr, "infer_embed_" + mode, None)):
-            raise ValueError(f"infer_mode={mode!r}: {type(tr).__name__} has no layer-wise inference (it covers "
-                             "SageTrainer on an unsharded device graph; sharded, GCN-family and unsupervised "
-                             "trainers infer with infer_mode='sampled')")
+            raise ValueError(f"infer_mode={mode!r}: {type(tr).__name__} has no layer-wise inference (layerwise covers "
+                             "SageTrainer and GcnTrainer, frontier SageTrainer, on an unsharded GPU graph; sharded, "
+                             "generic full-flow and unsupervised trainers infer with infer_mode='sampled')")
         return tr
 
     def _infer_fn(self, tr, what):

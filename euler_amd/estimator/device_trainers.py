@@ -112,10 +112,12 @@ STORE_AWARE = {"scalable"}
 
 
 def device_infers(model) -> bool:
-    """False for models whose evaluate / infer must stay on the engine path whatever the
-    trainer: layer-sampled GCNs (FastGCN / AdaptiveGCN draw their layers, reference
+    """False for models whose sampled evaluate / infer must stay on the engine path whatever
+    the trainer: layer-sampled GCNs (FastGCN / AdaptiveGCN draw their layers, reference
     fast_dataflow.py / layerwise_dataflow.py) — building a device trainer only to learn
-    that would also consume the engine's sampler stream before the engine-path eval."""
+    that would also consume the engine's sampler stream before the engine-path eval.
+    ``infer_mode="layerwise"`` does not ask (estimator/base.py _device_inference_trainer):
+    there they are plain GCNs over their metapath (GcnTrainer.infer_logits_layerwise)."""
     from euler_amd.dataflow import dataflows as D
 
     sampler = getattr(getattr(model, "gnn", None), "sampler", None)

@@ -324,6 +324,44 @@ class GcnTrainer(CapturedTrainer):
     def infer_embed(self, ids):
         return self.infer_logits(ids)[0]
 
+    # ------------------------------------------------------------------ layer-wise inference
+    def load_logical(self, sd):
+        super().load_logical(sd)
+        self._param_version = getattr(self, "_param_version", 0) + 1  # drops the cached layer-wise table
+
+    def layerwise(self):
+        """the :class:`LayerwiseGcnInference` of this trainer's current parameters; its cached
+        hidden table lives until the parameters change (a step, a load).  FastGCN and
+        AdaptiveGCN (``layer_draws``) sample layers only to train: here they are the plain
+        GCN over their metapath."""
+        from euler_amd.models.gcn_infer import LayerwiseGcnInference
+
+        key = (self.step_count, getattr(self, "_param_version", 0))
+        lw = getattr(self, "_lw", None)
+        if lw is None or self._lw_key != key:
+            convs = [c.fc.weight for c in self.gnn.convs]
+            fc, out_fc = (self.gnn.fc.weight, self.gnn.fc.bias), self.model.out_fc.weight
+            if lw is None:
+                lw = self._lw = LayerwiseGcnInference(self.graph, self.features, convs, self.masks,
+                                                      bool(self.gnn.sampler.add_self_loops), fc=fc, out_fc=out_fc)
+            else:
+                lw.set_weights(convs, fc, out_fc)
+            self._lw_key = key
+        return lw
+
+    @torch.no_grad()
+    def infer_logits_layerwise(self, ids):
+        """(embeddings [n, E], logits [n, C], labels [n, C]) of raw node ids by layer-wise
+        full-neighbourhood inference (models/gcn_infer.py): deterministic, normalised with the
+        graph's own degrees, so a node's row does not depend on the rest of the request.  Same
+        tuple and id handling as :meth:`infer_logits`."""
+        rows = self.graph.rows_of(ids).to(self.graph.device)
+        emb, logits = self.layerwise().logits(rows.clamp(min=0))
+        return emb, logits, self.labels[rows.clamp(min=0)]
+
+    def infer_embed_layerwise(self, ids):
+        return self.infer_logits_layerwise(ids)[0]
+
     # ------------------------------------------------------------------ oracle
     def reference_loss_and_grads_bf16(self):
         """The bf16-aware fp32 oracle of the last step, in pure CPU torch (no HIP op): the
