@@ -386,6 +386,12 @@ class GcnPlan : private PlanDict {
 
   void build_model() {
     const int64_t D = geti("D"), H0 = geti("H0"), H1 = L_ == 2 ? geti("H1") : 0, E = geti("E"), C = geti("C");
+    // "loss": "sigmoid" (the default: per-column cross-entropy, F1 counts) or "softmax" (row
+    // cross-entropy over exclusive classes, accuracy): the head kernel's instantiation
+    const std::string loss_name = has("loss") ? item("loss").cast<std::string>() : std::string("sigmoid");
+    TORCH_CHECK(loss_name == "sigmoid" || loss_name == "softmax",
+                "GcnPlan: loss must be \"sigmoid\" or \"softmax\", got \"", loss_name, "\"");
+    const bool softmax = loss_name == "softmax";
     feat_ = T("features");
     need_bf16_or_f32(feat_, -1, "features");
     TORCH_CHECK(feat_.dim() == 2 && feat_.size(0) == N_ && feat_.size(1) % 8 == 0 && feat_.size(1) >= D,
@@ -483,7 +489,8 @@ class GcnPlan : private PlanDict {
     a.C = static_cast<int32_t>(C);
     a.Cp = static_cast<int32_t>(Cp);
     a.labels = labels.data_ptr<float>();
-    a.inv_scale = 1.f / static_cast<float>(B_ * C);
+    a.loss = softmax ? kGcnLossSoftmax : kGcnLossSigmoid;
+    a.inv_scale = 1.f / static_cast<float>(softmax ? B_ : B_ * C);  // mean over rows / over elements
     part_w_ = zeros(nhead * last.outp * last.inp, torch::kFloat32);
     part_fc_ = zeros(nhead * Ep * last.outp, torch::kFloat32);
     part_bfc_ = zeros(nhead * Ep, torch::kFloat32);

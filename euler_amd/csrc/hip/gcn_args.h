@@ -17,8 +17,9 @@
 //             the in-block source degree (GCN norm) and resets the counter
 //   layer     (L = 2) the outer conv: edge-parallel weighted aggregation into LDS, MFMA
 //             linear + ReLU -> h1, the aggregate kept for dW
-//   head      the last conv + fc + out_fc + loss + the whole row-local backward + the
-//             weight-gradient partials of its rows + d(agg) of the roots (L = 2)
+//   head      the last conv + fc + out_fc + loss (sigmoid or softmax cross-entropy) + the
+//             whole row-local backward + the weight-gradient partials of its rows + d(agg) of
+//             the roots (L = 2)
 //   dw        (L = 2) d(W0) partials, one GEMM row per hop-0 edge: w_e (mask[s] . d agg[t])
 //             against the kept aggregate of s (d(h1) is never formed)
 //   reduce    the partials into the flat fp32 gradient, loss / F1 counts, epoch + 1
@@ -175,6 +176,11 @@ struct GcnLayerArgs {  // the outer conv (L = 2): targets S_1, sources S_2
   uint16_t* agg_out;    // [cap_t][lin.inp] bf16 aggregate (dW operand)
 };
 
+// the head's loss (GcnHeadArgs.loss): per-column sigmoid cross-entropy + micro-F1 counts
+// (multi-label, the reference's), or row softmax cross-entropy + accuracy (single-label)
+constexpr int kGcnLossSigmoid = 0;
+constexpr int kGcnLossSoftmax = 1;
+
 struct GcnHeadArgs {  // targets: the B roots; sources: S_1
   GcnAggSrc src;
   const int32_t* enode; // hop 0 neighbour node ids (L = 1: by-id source rows)
@@ -194,8 +200,10 @@ struct GcnHeadArgs {  // targets: the B roots; sources: S_1
   const float* bfc;     // [E]
   const float* wout;    // [C][E] fp32 (no bias: reference out_fc)
   int32_t E, Ep, C, Cp;
-  const float* labels;  // [N][C] dense multi-label targets
-  float inv_scale;      // 1 / (B C)
+  const float* labels;  // [N][C] dense targets (softmax: a one-hot row, or a non-negative
+                        // row = a target distribution up to its sum)
+  int32_t loss;         // kGcnLossSigmoid / kGcnLossSoftmax
+  float inv_scale;      // sigmoid: 1 / (B C); softmax: 1 / B
   float* dagg;          // L = 2: [B][lin.inp] fp32 d(agg) of the roots, gcn_dw's input (nullptr: L = 1)
   float* dbg_agg;       // diagnostics (nullptr in the step): [B][KP] the roots' fp32 aggregates
   int64_t* ostep_inc;   // fused optimizer step: block 0 advances the optimizer's step count
@@ -204,7 +212,7 @@ struct GcnHeadArgs {  // targets: the B roots; sources: S_1
   float* part_fc;       // [nblk][Ep][outp]    d(fc W)
   float* part_bfc;      // [nblk][Ep]
   float* part_out;      // [nblk][Cp][Ep]      d(out_fc W)
-  float* part_stat;     // [nblk][4] loss, tp, fp, fn
+  float* part_stat;     // [nblk][4] loss, tp, fp, fn (softmax: correct, wrong, wrong rows)
   long long* prof;      // optional [nblk][16] wall-clock stamps of the phases (diagnostics)
 };
 

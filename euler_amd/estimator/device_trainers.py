@@ -165,7 +165,8 @@ def _check_loss(model, tr):
     """never train a ``loss="softmax"`` model with a trainer whose head is the sigmoid one"""
     if getattr(model, "loss", "sigmoid") == "softmax" and not getattr(tr, "trains_softmax", False):
         raise ValueError(f"{type(tr).__name__} has no softmax loss: loss='softmax' trains on the device path "
-                         "through SageTrainer (SupervisedGraphSage) or the generic flow trainers")
+                         "through SageTrainer (SupervisedGraphSage), GcnTrainer (the fused GCN family) or the "
+                         "generic flow trainers")
 
 
 def build_device_trainer(est, model, first):
@@ -186,7 +187,9 @@ def build_device_trainer(est, model, first):
             est._prepare(first, build_optimizer=False)
             tr = builder(Ctx(est, model))
             _check_loss(model, tr)
-            tr.device_trainer_kind = name
+            # a builder that chooses between trainers names its choice itself ("gcn": the fused
+            # GcnTrainer of the "full_flow" entry)
+            tr.device_trainer_kind = getattr(tr, "device_trainer_kind", None) or name
             return tr
     if stores:
         raise NoDeviceTrainer(f"{type(model).__name__} holds a historical-embedding (Scalable*) encoder that no "
@@ -304,9 +307,10 @@ def build_sharded_trainer(est, model, first):
 
             if c.params.get("gcn_fused", True) and GcnTrainer.supports(model, g.local, c.batch):
                 tr = GcnTrainer.from_model(model, g.local, c.batch, caps=caps, **c.opt_kw())
+                tr.device_trainer_kind = "gcn"
             else:
                 tr = FullFlowTrainer.from_model(model, g.local, c.batch, **c.opt_kw(), caps=caps)
-            tr.device_trainer_kind = "full_flow"
+                tr.device_trainer_kind = "full_flow"
             return tr
         tr = ShardedFlowTrainer.from_model(model, g, c.batch, caps=caps, **c.opt_kw())
         tr.device_trainer_kind = "sharded_full_flow"
@@ -618,8 +622,10 @@ def _full(c: Ctx):
     g = _supervised_upload(c)
     caps = c.params.get("device_flow_caps", "bounded")
     if c.params.get("gcn_fused", True) and GcnTrainer.supports(c.model, g, c.batch):
-        # SupervisedGCN-shaped: the fused hand-written step (models/gcn_trainer.py)
-        return GcnTrainer.from_model(c.model, g, c.batch, caps=caps, **c.opt_kw())
+        # SupervisedGCN-shaped, either loss: the fused hand-written step (models/gcn_trainer.py)
+        tr = GcnTrainer.from_model(c.model, g, c.batch, caps=caps, **c.opt_kw())
+        tr.device_trainer_kind = "gcn"
+        return tr
     return FullFlowTrainer.from_model(c.model, g, c.batch, **c.opt_kw(), caps=caps)
 
 

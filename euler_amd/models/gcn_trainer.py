@@ -39,6 +39,11 @@ launches plus one per sampled hop: ``gcn_layer_draw`` stamps the step's layer (t
 it (per target: the kept count for the offsets, then one wave per target compacts its
 neighbour list with a ballot).
 
+``loss="softmax"`` models (single-label data: exclusive classes) take the head's softmax
+instantiation (``csrc/hip/gcn_head_softmax.hip``: row cross-entropy, a row's logits tiles merged
+across the block's waves) and report accuracy in the same three counts; FastGCN and AdaptiveGCN
+ride the same head.  Every other launch is the sigmoid step's.
+
 Capacities: the flow's edge / node-set caps come from ``dataflow/device_flow.py``
 (``"bounded"`` by default through the estimator); a batch beyond them sets the overflow
 word, and the estimator rolls the chunk back, grows the caps and re-plans.
@@ -119,12 +124,19 @@ def _gcn_shape(model):
 
 
 class GcnTrainer(CapturedTrainer):
-    metric_name = "f1"
+    trains_softmax = True  # estimator/device_trainers.py _check_loss
 
     def __init__(self, model, graph, batch_size, masks, caps="bounded", optimizer="adam", learning_rate=0.01,
                  layer_draws=None):
         if graph.device.type != "cuda":
             raise ValueError("the fused GCN step runs on the GPU (the generic FullFlowTrainer covers the CPU)")
+        # "sigmoid": per-column binary cross-entropy + micro-F1 (multi-label, the reference's);
+        # "softmax": row cross-entropy + accuracy (single-label: exclusive classes) — the head's
+        # other instantiation (plan key "loss"); the counts then hold correct / wrong / wrong rows
+        self.loss_name = getattr(model, "loss", "sigmoid")
+        if self.loss_name not in ("sigmoid", "softmax"):
+            raise ValueError(f"loss must be 'sigmoid' or 'softmax', got {self.loss_name!r}")
+        self.metric_name = "acc" if self.loss_name == "softmax" else "f1"
         self.gnn = model.gnn
         self.graph = graph
         self.B = int(batch_size)
@@ -155,12 +167,9 @@ class GcnTrainer(CapturedTrainer):
     def supports(model, graph=None, batch_size=None) -> bool:
         """SupervisedGCN-shaped: 1-2 bias-free GCNConvs on GCNDataFlow with self loops, fc with
         bias, out_fc without; conv widths <= 64, inputs <= 128, fc / label widths <= 128.
-        Sigmoid models only: the fused GCN head (csrc/hip/gcn.hip, and graph_cls.hip of the
-        graph classifiers) has no softmax loss, so a ``loss="softmax"`` model trains on the
-        generic :class:`FullFlowTrainer`."""
+        Both losses: ``loss="softmax"`` models (single-label data) take the head's softmax
+        instantiation (csrc/hip/gcn.hip) and report accuracy."""
         if os.environ.get("EULER_AMD_GCN_FUSED", "1") == "0":
-            return False
-        if getattr(model, "loss", "sigmoid") != "sigmoid":
             return False
         convs = _gcn_shape(model)
         if convs is None:
@@ -239,7 +248,8 @@ class GcnTrainer(CapturedTrainer):
              "wfc": self.gnn.fc.weight.detach(), "g_wfc": self.gnn.fc.weight.grad,
              "bfc": self.gnn.fc.bias.detach(), "g_bfc": self.gnn.fc.bias.grad,
              "wout": m.out_fc.weight.detach(), "g_wout": m.out_fc.weight.grad,
-             "loss_out": self.loss_out, "counts": self.counts, "layer_draws": self.layer_draws}
+             "loss_out": self.loss_out, "counts": self.counts, "layer_draws": self.layer_draws,
+             "loss": self.loss_name}
         if L == 2:
             d.update({"H1": int(w[1].shape[0]), "w1": w[1].detach(), "g_w1": w[1].grad})
         self._buf = d  # the plan's dict, kept like SageTrainer's
@@ -293,6 +303,8 @@ class GcnTrainer(CapturedTrainer):
 
     # ------------------------------------------------------------------ metric
     def metric(self) -> float:
+        """streaming micro-F1 since the last :meth:`reset_metric`; under ``loss="softmax"`` the
+        row accuracy (the counts are correct / wrong / wrong rows: this formula is correct / rows)"""
         tp, fp, fn = self.counts.tolist()
         return 2.0 * tp / max(2.0 * tp + fp + fn, 1e-12)
 
@@ -376,6 +388,8 @@ class GcnTrainer(CapturedTrainer):
           h = bf(relu(agg W^T)) (the outer conv's h1 kept bf16 for the next hop);
         * head: emb = bf(h Wfc^T + bfc), logits = emb Wout^T (fp32),
           d = bf((sigmoid - y) / (B C)), demb = d Wout, dz = bf(relu'(h) (bf(demb) Wfc));
+          ``loss="softmax"``: loss = sum y (logsumexp(logits) - logits) / B and
+          d = bf((s softmax(logits) - y) / B), s = the label row's sum (1 for a one-hot row);
           dWout = d^T emb, dWfc = bf(demb)^T h, dbfc = sum demb, dW = dz^T agg;
         * L = 2: dagg = dz W (fp32); per hop-0 edge e: bf(relu'(h1_s) w_e dagg_t) against
           agg1_s (gcn_dw_kernel: d h1 is never formed).
@@ -438,8 +452,13 @@ class GcnTrainer(CapturedTrainer):
         emb = bf(H0 @ Wfc.t() + bfc)
         logits = emb @ Wout.t()
         y = self.labels[roots.to(self.labels.device)].to(cpu).float()
-        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, y)
-        d = bf((torch.sigmoid(logits) - y) / float(y.numel()))
+        if self.loss_name == "softmax":
+            s = y.sum(1, keepdim=True)
+            loss = (y * (torch.logsumexp(logits, 1, keepdim=True) - logits)).sum() / float(B)
+            d = bf((s * torch.softmax(logits, 1) - y) / float(B))
+        else:
+            loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, y)
+            d = bf((torch.sigmoid(logits) - y) / float(y.numel()))
         demb = d @ Wout
         De = bf(demb)
         dz = bf((H0 > 0).to(f32) * (De @ Wfc))
