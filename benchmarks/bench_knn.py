@@ -12,8 +12,16 @@ against the flat index of the same implementation.
 the argument) and touches nothing but ``build_index`` / ``search``, so with ``--tool-file``
 pointing at another checkout's ``euler_amd/tools/knn.py`` the same script times that one.
 
+``--dtype bf16`` compares the two table dtypes of this tree instead: the embeddings are rounded
+to bf16 so that both routes see the same numbers, one index of ``--index`` is built per dtype
+(the IVF ones share their centroids), and the fp32 and bf16 searches are timed alternating in one
+process, ``--reps`` repetitions of ``--iters`` searches each.  It prints one JSON line with, per
+route, the median and the spread of the time per search, the peak bytes allocated during a
+search, the bytes the index holds, and how far the two results agree.
+
     python benchmarks/bench_knn.py [--n 1000000] [--d 128] [--nq 1024] [--k 10]
         [--index flat|ivfflat] [--impl kernel|torch] [--tool-file PATH]
+        [--dtype fp32|bf16] [--reps 5] [--iters 10]
 """
 import argparse
 import importlib.util
@@ -38,6 +46,68 @@ def _clustered(n, d, centres, gen, dev, torch):
     return out
 
 
+def _compare_dtypes(a, knn, x, q, torch, np):
+    """fp32 and bf16 indexes over the same bf16-representable values, searched alternating"""
+    xb = x.to(torch.bfloat16)
+    q = q.to(torch.bfloat16).float()
+    x = None  # the fp32 route's table is made from the rounded values below
+    routes = {}
+    for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        table = xb.float() if name == "fp32" else xb
+        if a.index == "flat":
+            idx = knn.FlatIndex(a.d, device="cuda", dtype=dt)
+        else:
+            idx = knn.IVFFlatIndex(a.d, int(4 * a.n ** 0.5), nprobe=10, device="cuda", dtype=dt)
+            if routes:
+                idx.cent, idx.ncent = routes["fp32"]["index"].cent, routes["fp32"]["index"].ncent
+            else:
+                g = torch.Generator(device="cpu").manual_seed(1234)
+                keep = torch.randperm(a.n, generator=g)[:256 * idx.ncent].sort().values.cuda()
+                idx.train(table[keep] if keep.numel() < a.n else table)
+        idx.add(table)
+        torch.cuda.synchronize()
+        held = sum(t.numel() * t.element_size() for t in (idx.xb, getattr(idx, "xs", None)) if t is not None)
+        routes[name] = {"index": idx, "build_s": time.perf_counter() - t0, "index_bytes": held,
+                        "build_peak_bytes": torch.cuda.max_memory_allocated() - before, "ms": []}
+        del table
+    for r in routes.values():
+        r["out"] = r["index"].search(q, a.k)  # warm-up
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        r["index"].search(q, a.k)
+        torch.cuda.synchronize()
+        r["peak"] = torch.cuda.max_memory_allocated() - before
+    for _ in range(a.reps):
+        for r in routes.values():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                r["index"].search(q, a.k)
+            torch.cuda.synchronize()
+            r["ms"].append((time.perf_counter() - t0) * 1e3 / a.iters)
+    (D0, I0), (D1, I1) = routes["fp32"]["out"], routes["bf16"]["out"]
+    fin = np.isfinite(D0) & np.isfinite(D1)
+    res = {"bench": "knn_dtypes", "index": a.index, "n": a.n, "d": a.d, "nq": a.nq, "k": a.k, "reps": a.reps,
+           "iters": a.iters, "same_rows": round(float((I0 == I1).mean()), 6),
+           "max_abs_dist_diff": float(np.abs(D0[fin] - D1[fin]).max()) if fin.any() else 0.0,
+           "device": torch.cuda.get_device_name(0)}
+    for name, r in routes.items():
+        ms = statistics.median(r["ms"])
+        res[name] = {"search_ms": round(ms, 3), "search_ms_min": round(min(r["ms"]), 3),
+                     "search_ms_max": round(max(r["ms"]), 3), "search_ms_all": [round(t, 3) for t in r["ms"]],
+                     "queries_per_s": round(a.nq / (ms * 1e-3), 1), "search_peak_bytes": int(r["peak"]),
+                     "index_bytes": int(r["index_bytes"]), "build_s": round(r["build_s"], 4),
+                     "build_peak_bytes": int(r["build_peak_bytes"])}
+    res["bf16_over_fp32_time"] = round(res["bf16"]["search_ms"] / res["fp32"]["search_ms"], 4)
+    print(json.dumps(res))
+    return res
+
+
 def main(argv=None):
     import numpy as np
     import torch
@@ -52,6 +122,10 @@ def main(argv=None):
     ap.add_argument("--tool-file", dest="tool_file", default=None,
                     help="load build_index from this knn.py instead of euler_amd.tools.knn")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
+                    help="bf16: time the fp32 and the bf16 table of this tree against each other")
+    ap.add_argument("--reps", type=int, default=5, help="--dtype bf16: repetitions per route, alternating")
+    ap.add_argument("--iters", type=int, default=10, help="--dtype bf16: searches per repetition")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_knn measures on a GPU; none is available")
@@ -75,6 +149,10 @@ def main(argv=None):
     centres = torch.randn(1024, a.d, generator=gen, device=dev) * 4.0
     x = _clustered(a.n, a.d, centres, gen, dev, torch)
     q = _clustered(a.nq, a.d, centres, gen, dev, torch)
+    if a.dtype == "bf16":
+        if a.tool_file or a.impl != "kernel":
+            raise SystemExit("--dtype bf16 compares the kernels of this tree (no --tool-file, --impl kernel)")
+        return _compare_dtypes(a, knn, x, q, torch, np)
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()

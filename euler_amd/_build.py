@@ -217,7 +217,7 @@ def build_plan_selftest() -> str:
 # their arithmetic compiles to scalar fmac only.  It changes no summation order, only which
 # products are fused; gcn_csr.hip takes 121-123 VGPRs this way against 124-125 with them
 # (profiles/gcn_infer/resource_usage.txt quotes this build line)
-NO_PACKED_FP32 = {"gcn_csr.hip", "gcn_head_softmax.hip"}
+NO_PACKED_FP32 = {"gcn_csr.hip", "gcn_head_softmax.hip", "knn_bf16.hip"}
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

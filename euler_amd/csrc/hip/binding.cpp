@@ -543,6 +543,8 @@ PYBIND11_MODULE(_hip_ops, m) {
   register_frontier_ops(f);
   auto gc = m.def_submodule("gcn_csr");
   register_gcn_csr_ops(gc);
+  auto kb = m.def_submodule("knn_bf16");
+  register_knn_bf16_ops(kb);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

@@ -1,4 +1,4 @@
-// torch binding of the k-nearest-neighbour kernels (knn.hip).  Host-only; operands go through
+// torch binding of the k-nearest-neighbour kernels (knn.hip, knn_bf16.hip).  Host-only; operands go through
 // binding_util.h (rules R1-R3 there).  The outputs are allocated here, never inside a launcher.
 #include "hip/binding_util.h"
 #include "hip/launchers.h"
@@ -90,7 +90,92 @@ std::vector<torch::Tensor> knn_merge(torch::Tensor pd, torch::Tensor pr, torch::
   return {D, I};
 }
 
+const uint16_t* bf_ptr(const torch::Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
+
+// ||x_i||^2 [n] fp32 of a bf16 table, read in place
+torch::Tensor knn_row_norms_bf16(torch::Tensor x) {
+  const Operands c("knn_row_norms_bf16", x, "x");
+  c.bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(1) <= INT32_MAX,
+              "knn_row_norms_bf16: x must be [n >= 1, d >= 1]");
+  const auto g = c.guard();
+  auto xn = torch::empty({x.size(0)}, x.options().dtype(torch::kFloat32));
+  launch_ok(eh_knn_row_norms_bf16(bf_ptr(x), x.size(0), static_cast<int>(x.size(1)), xn.data_ptr<float>(),
+                                  cur_stream()),
+            "knn_row_norms_bf16");
+  return xn;
+}
+
+// knn_flat_scan over a bf16 table and bf16 queries, both read in place; fp32 / int64 partials
+std::vector<torch::Tensor> knn_flat_scan_bf16(torch::Tensor q, torch::Tensor x, torch::Tensor xn, int64_t k,
+                                              int64_t splits) {
+  const Operands c("knn_flat_scan_bf16", q, "q");
+  c.bf16(q, "q");
+  c.bf16(x, "x");
+  c.f32(xn, "xn");
+  TORCH_CHECK(q.dim() == 2 && x.dim() == 2 && q.size(1) == x.size(1) && q.size(1) >= 1,
+              "knn_flat_scan_bf16: q [nq, d] and x [n, d] must share d >= 1");
+  TORCH_CHECK(q.size(0) >= 1 && x.size(0) >= 1, "knn_flat_scan_bf16: empty q or x");
+  TORCH_CHECK(xn.dim() == 1 && xn.numel() == x.size(0), "knn_flat_scan_bf16: xn must be [n]");
+  TORCH_CHECK(q.size(1) <= INT32_MAX, "knn_flat_scan_bf16: d too large");
+  check_k(k);
+  TORCH_CHECK(splits >= 1 && splits <= eh_knn_max_splits(), "knn_flat_scan_bf16: splits must be in [1, ",
+              eh_knn_max_splits(), "]");
+  const auto g = c.guard();
+  const int64_t nq = q.size(0);
+  auto pd = torch::empty({nq, splits, k}, xn.options());
+  auto pr = torch::empty({nq, splits, k}, xn.options().dtype(torch::kInt64));
+  launch_ok(eh_knn_flat_scan_bf16(bf_ptr(q), bf_ptr(x), xn.data_ptr<float>(), nq, x.size(0),
+                                  static_cast<int>(q.size(1)), static_cast<int>(k), static_cast<int>(splits),
+                                  pd.data_ptr<float>(), pr.data_ptr<int64_t>(), cur_stream()),
+            "knn_flat_scan_bf16");
+  return {pd, pr};
+}
+
+// knn_ivf_scan over a bf16 list-ordered table
+std::vector<torch::Tensor> knn_ivf_scan_bf16(torch::Tensor q, torch::Tensor xs, torch::Tensor xn,
+                                             torch::Tensor list_ptr, torch::Tensor row_of, torch::Tensor probe,
+                                             int64_t k) {
+  const Operands c("knn_ivf_scan_bf16", q, "q");
+  c.bf16(q, "q");
+  c.bf16(xs, "xs");
+  c.f32(xn, "xn");
+  c.i64(list_ptr, "list_ptr");
+  c.i64(row_of, "row_of");
+  c.i64(probe, "probe");
+  TORCH_CHECK(q.dim() == 2 && xs.dim() == 2 && q.size(1) == xs.size(1) && q.size(1) >= 1,
+              "knn_ivf_scan_bf16: q [nq, d] and xs [n, d] must share d >= 1");
+  TORCH_CHECK(q.size(1) <= INT32_MAX, "knn_ivf_scan_bf16: d too large");
+  const int64_t nq = q.size(0), n = xs.size(0);
+  TORCH_CHECK(nq >= 1, "knn_ivf_scan_bf16: empty q");
+  TORCH_CHECK(xn.dim() == 1 && xn.numel() == n && row_of.dim() == 1 && row_of.numel() == n,
+              "knn_ivf_scan_bf16: xn and row_of must be [n]");
+  TORCH_CHECK(list_ptr.dim() == 1 && list_ptr.numel() >= 2, "knn_ivf_scan_bf16: list_ptr must be [ncent + 1]");
+  TORCH_CHECK(probe.dim() == 2 && probe.size(0) == nq && probe.size(1) >= 1 && probe.size(1) <= eh_knn_max_splits(),
+              "knn_ivf_scan_bf16: probe must be [nq, nprobe] with nprobe in [1, ", eh_knn_max_splits(), "]");
+  check_k(k);
+  const auto g = c.guard();
+  const int64_t nprobe = probe.size(1);
+  auto pd = torch::empty({nq, nprobe, k}, xn.options());
+  auto pr = torch::empty({nq, nprobe, k}, xn.options().dtype(torch::kInt64));
+  launch_ok(eh_knn_ivf_scan_bf16(bf_ptr(q), bf_ptr(xs), xn.data_ptr<float>(), list_ptr.data_ptr<int64_t>(),
+                                 row_of.data_ptr<int64_t>(), probe.data_ptr<int64_t>(), nq, n, list_ptr.numel() - 1,
+                                 static_cast<int>(nprobe), static_cast<int>(q.size(1)), static_cast<int>(k),
+                                 pd.data_ptr<float>(), pr.data_ptr<int64_t>(), cur_stream()),
+            "knn_ivf_scan_bf16");
+  return {pd, pr};
+}
+
 }  // namespace
+
+// the searches over bf16 tables (knn_bf16.hip), on the submodule _hip_ops.knn_bf16
+void register_knn_bf16_ops(py::module& m) {
+  m.def("row_norms", &knn_row_norms_bf16, py::arg("x"));
+  m.def("flat_scan", &knn_flat_scan_bf16, py::arg("q"), py::arg("x"), py::arg("xn"), py::arg("k"),
+        py::arg("splits"));
+  m.def("ivf_scan", &knn_ivf_scan_bf16, py::arg("q"), py::arg("xs"), py::arg("xn"), py::arg("list_ptr"),
+        py::arg("row_of"), py::arg("probe"), py::arg("k"));
+}
 
 void register_knn_ops(py::module& m) {
   m.def("knn_flat_scan", &knn_flat_scan, py::arg("q"), py::arg("x"), py::arg("xn"), py::arg("k"), py::arg("splits"));

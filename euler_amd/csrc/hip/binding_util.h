@@ -49,6 +49,9 @@ void register_frontier_ops(py::module& m);
 // binding_gcn_csr.cpp: full-neighbourhood GCN-family layer over the graph's CSR and its degree
 // counts (registered on the submodule _hip_ops.gcn_csr)
 void register_gcn_csr_ops(py::module& m);
+// binding_knn.cpp: the searches over bf16 tables, knn_bf16.hip (registered on the submodule
+// _hip_ops.knn_bf16; partials go to knn_merge of register_knn_ops)
+void register_knn_bf16_ops(py::module& m);
 
 namespace euler_bind {
 

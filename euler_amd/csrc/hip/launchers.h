@@ -234,6 +234,16 @@ hipError_t eh_knn_ivf_scan(const float* Q, const float* XS, const float* xn, con
 hipError_t eh_knn_merge(const float* pd, const int64_t* pr, const float* qn, int64_t nq, int S, int k, float* D,
                         int64_t* I, hipStream_t s);
 
+// knn_bf16.hip (the same searches over bf16 tables read in place: Q / X / XS are raw bf16 bits,
+// xn and the partials stay fp32 / int64, so eh_knn_merge serves both; same limits on k and S)
+hipError_t eh_knn_flat_scan_bf16(const uint16_t* Q, const uint16_t* X, const float* xn, int64_t nq, int64_t n, int d,
+                                 int k, int S, float* pd, int64_t* pr, hipStream_t s);
+hipError_t eh_knn_ivf_scan_bf16(const uint16_t* Q, const uint16_t* XS, const float* xn, const int64_t* list_ptr,
+                                const int64_t* row_of, const int64_t* probe, int64_t nq, int64_t n, int64_t ncent,
+                                int nprobe, int d, int k, float* pd, int64_t* pr, hipStream_t s);
+// xn [n] = sum_c x[i, c]^2 in fp32
+hipError_t eh_knn_row_norms_bf16(const uint16_t* X, int64_t n, int d, float* xn, hipStream_t s);
+
 // sage_csr.hip (full-neighbourhood GraphSAGE layer over the graph's own CSR: weight-normalised
 // mean of x over the masked (row, type) segments, then act([x_self | ns * mean + ss * x_self] @ W^T)).
 // x [N, Dp] bf16 / fp32 (Dp % 16 == 0, <= 512), W [Hp, 2 Dp] bf16 row-major (Hp % 64 == 0),

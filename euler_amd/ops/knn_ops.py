@@ -9,8 +9,8 @@ Ordering rule: results are ordered by the pair (squared distance, original row),
 so equal distances go to the lower row.  The ranking key is ``s = ||x||^2 - 2 q.x``; the
 distance is ``max(s + ||q||^2, 0)``.  Missing results are ``inf`` / ``-1``.
 
-On GPU tensors the ops run hand-written gfx950 kernels (``csrc/hip/knn.hip``): a scan
-kernel writes, per (query, split), a sorted partial list ``dist [nq, S, k]`` fp32 /
+On GPU tensors the ops run hand-written gfx950 kernels (``csrc/hip/knn.hip`` for fp32 tables,
+``csrc/hip/knn_bf16.hip`` for bf16 tables): a scan kernel writes, per (query, split), a sorted partial list ``dist [nq, S, k]`` fp32 /
 ``row [nq, S, k]`` int64, and a merge kernel combines the ``S`` partials.  No
 ``[nq, n]`` distance matrix is ever allocated.  CPU tensors (and ``k`` above the kernels'
 limit of 128) take the pure-torch twin below, which follows the same ordering rule and is
@@ -20,6 +20,12 @@ Inverted lists are a CSR: ``xs`` is the database permuted so that list ``l`` is 
 ``list_ptr[l]:list_ptr[l + 1]``, ``row_of[p]`` is the original row of position ``p``.
 Inside a list the positions must be in ascending original-row order (a stable sort by
 list gives that); ties inside a list are then decided by position.
+
+The table's dtype picks the path.  A bfloat16 ``x`` / ``xs`` is searched in place, with bf16
+matrix instructions and fp32 sums (exact products, so the result is that of fp32 arithmetic
+on the bf16 values); no fp32 copy of the table is made, on the GPU or in the twin.  Its
+queries are bf16: an fp32 ``q`` is rounded to bf16 once, and the distances (``||q||^2``
+included) are those of the rounded query.  A float32 table takes the fp32 kernels.
 """
 from __future__ import annotations
 
@@ -27,7 +33,7 @@ import torch
 
 from euler_amd.ops._native import hip, use_hip
 
-__all__ = ["flat_topk", "ivf_topk", "nearest", "build_lists", "MAX_KERNEL_K"]
+__all__ = ["flat_topk", "ivf_topk", "nearest", "build_lists", "row_norms", "MAX_KERNEL_K"]
 
 MAX_KERNEL_K = 128
 _MAX_SPLITS = 64
@@ -42,16 +48,39 @@ def _norms(x):
     return (x * x).sum(1)
 
 
+_TWIN_ROWS = 1 << 16  # rows of a bf16 table the twin holds in fp32 at a time
+
+
+def _norms_bf16(x):
+    """||x_i||^2 in fp32 of a bf16 table without an fp32 copy of it"""
+    if x.shape[0] and use_hip(x):
+        return hip().knn_bf16.row_norms(x)
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    for r0 in range(0, x.shape[0], _TWIN_ROWS):
+        out[r0:r0 + _TWIN_ROWS] = _norms(x[r0:r0 + _TWIN_ROWS].float())
+    return out
+
+
+def row_norms(x):
+    """``||x_i||^2 [n]`` in fp32; a bfloat16 table is read in place (the ``knn_row_norms_bf16`` kernel on the
+    GPU, row chunks on the CPU)"""
+    return _norms_bf16(x.contiguous()) if x.dtype == torch.bfloat16 else _norms(_f32(x))
+
+
+def _bf16(t):
+    return t.to(torch.bfloat16).contiguous()
+
+
 def _empty_result(nq, k, device):
     return (torch.full((nq, k), float("inf"), device=device),
             torch.full((nq, k), -1, dtype=torch.long, device=device))
 
 
-def _auto_splits(nq, n, k):
+def _auto_splits(nq, n, k, tile_rows=64):
     tq = 128 if k <= 32 else 64
     nqt = -(-nq // tq)
     s = -(-_TARGET_BLOCKS // nqt)
-    tiles = -(-n // 64)
+    tiles = -(-n // tile_rows)
     return int(max(1, min(s, _MAX_SPLITS, tiles // 8)))
 
 
@@ -72,6 +101,25 @@ def _flat_topk_torch(q, x, k, xn):
     return D, I
 
 
+def _flat_topk_torch_bf16(q, x, k, xn):
+    """the twin over a bf16 table: fp32 arithmetic on the bf16 values, the table upcast
+    ``_TWIN_ROWS`` rows at a time"""
+    nq, n = q.shape[0], x.shape[0]
+    D, I = _empty_result(nq, k, q.device)
+    kk = min(k, n)
+    q = q.float()
+    chunk = max(1, min(nq, (1 << 26) // max(n, 1)))
+    for s0 in range(0, nq, chunk):
+        qq = q[s0:s0 + chunk]
+        s = torch.empty(qq.shape[0], n, device=q.device)
+        for r0 in range(0, n, _TWIN_ROWS):
+            s[:, r0:r0 + _TWIN_ROWS] = xn[r0:r0 + _TWIN_ROWS].unsqueeze(0) - 2.0 * (qq @ x[r0:r0 + _TWIN_ROWS].float().t())
+        v, i = torch.sort(s, dim=1, stable=True)
+        D[s0:s0 + chunk, :kk] = (v[:, :kk] + _norms(qq).unsqueeze(1)).clamp_min_(0.0)
+        I[s0:s0 + chunk, :kk] = i[:, :kk]
+    return D, I
+
+
 def _ivf_topk_torch(q, xs, list_ptr, row_of, probe, k, xn):
     nq = q.shape[0]
     ncent = list_ptr.numel() - 1
@@ -82,7 +130,7 @@ def _ivf_topk_torch(q, xs, list_ptr, row_of, probe, k, xn):
         pos = torch.cat(pos) if pos else torch.zeros(0, dtype=torch.long, device=q.device)
         if pos.numel() == 0:
             continue
-        s = xn[pos] - 2.0 * (xs[pos] @ q[i])
+        s = xn[pos] - 2.0 * (xs[pos].float() @ q[i])  # a bf16 table is upcast over the probed rows only
         rows = row_of[pos]
         o = torch.argsort(rows, stable=True)
         o = o[torch.argsort(s[o], stable=True)][:k]
@@ -94,10 +142,14 @@ def _ivf_topk_torch(q, xs, list_ptr, row_of, probe, k, xn):
 def flat_topk(q, x, k, xn=None, splits=None):
     """``(D [nq, k] fp32, I [nq, k] int64)``: the k nearest rows of ``x [n, d]`` for each row of
     ``q [nq, d]``.  ``xn`` is ``||x||^2`` per row if the caller has it; ``splits`` fixes the
-    number of row ranges scanned in parallel (default: enough to fill the chip)."""
+    number of row ranges scanned in parallel (default: enough to fill the chip).  A bfloat16
+    ``x`` is searched in place with bf16 queries (an fp32 ``q`` is rounded to bf16 once; ``D``
+    is the distance to the rounded query); see the module docstring."""
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")
+    if x.dtype == torch.bfloat16:
+        return _flat_topk_bf16(q, x, k, xn, splits)
     q, x = _f32(q), _f32(x)
     if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1]:
         raise ValueError("flat_topk: q [nq, d] and x [n, d] must share d")
@@ -113,6 +165,22 @@ def flat_topk(q, x, k, xn=None, splits=None):
     return D, I
 
 
+def _flat_topk_bf16(q, x, k, xn, splits):
+    q, x = _bf16(q), x.contiguous()
+    if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1]:
+        raise ValueError("flat_topk: q [nq, d] and x [n, d] must share d")
+    nq, n = q.shape[0], x.shape[0]
+    if nq == 0 or n == 0:
+        return _empty_result(nq, k, q.device)
+    xn = _norms_bf16(x) if xn is None else _f32(xn)
+    if not use_hip(q, x, xn) or k > MAX_KERNEL_K:
+        return _flat_topk_torch_bf16(q, x, k, xn)
+    s = _auto_splits(nq, n, k, tile_rows=128) if splits is None else int(splits)
+    pd, pr = hip().knn_bf16.flat_scan(q, x, xn, k, s)
+    D, I = hip().knn_merge(pd, pr, _norms(q.float()))
+    return D, I
+
+
 def nearest(q, x, xn=None):
     """index of the nearest row of ``x`` per query (the lowest one among equals)"""
     return flat_topk(q, x, 1, xn=xn)[1][:, 0]
@@ -120,12 +188,18 @@ def nearest(q, x, xn=None):
 
 def ivf_topk(q, xs, list_ptr, row_of, probe, k, xn=None):
     """``(D, I)`` over the lists in ``probe [nq, nprobe]`` (``-1``: none); ``I`` holds
-    original rows.  See the module docstring for the CSR layout."""
+    original rows.  See the module docstring for the CSR layout; a bfloat16 ``xs`` is searched in
+    place with bf16 queries (an fp32 ``q`` is rounded to bf16 once)."""
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")
-    q, xs = _f32(q), _f32(xs)
-    xn = _norms(xs) if xn is None else _f32(xn)
+    bf = xs.dtype == torch.bfloat16
+    if bf:
+        q, xs = _bf16(q), xs.contiguous()
+        xn = _norms_bf16(xs) if xn is None else _f32(xn)
+    else:
+        q, xs = _f32(q), _f32(xs)
+        xn = _norms(xs) if xn is None else _f32(xn)
     list_ptr, row_of, probe = list_ptr.long().contiguous(), row_of.long().contiguous(), probe.long().contiguous()
     if q.dim() != 2 or xs.dim() != 2 or q.shape[1] != xs.shape[1]:
         raise ValueError("ivf_topk: q [nq, d] and xs [n, d] must share d")
@@ -134,9 +208,10 @@ def ivf_topk(q, xs, list_ptr, row_of, probe, k, xn=None):
     if q.shape[0] == 0 or probe.shape[1] == 0:
         return _empty_result(q.shape[0], k, q.device)
     if not use_hip(q, xs, xn, list_ptr, row_of, probe) or k > MAX_KERNEL_K or probe.shape[1] > _MAX_SPLITS:
-        return _ivf_topk_torch(q, xs, list_ptr, row_of, probe, k, xn)
-    pd, pr = hip().knn_ivf_scan(q, xs, xn, list_ptr, row_of, probe, k)
-    return tuple(hip().knn_merge(pd, pr, _norms(q)))
+        return _ivf_topk_torch(q.float(), xs, list_ptr, row_of, probe, k, xn)
+    scan = hip().knn_bf16.ivf_scan if bf else hip().knn_ivf_scan
+    pd, pr = scan(q, xs, xn, list_ptr, row_of, probe, k)
+    return tuple(hip().knn_merge(pd, pr, _norms(q.float())))
 
 
 def build_lists(assign, ncent):

@@ -14,10 +14,16 @@ no distance matrix is allocated, equal distances go to the lower row, the invert
 are a CSR).  CPU tensors, and ``use_kernels=False`` on any device, take the torch
 composition: GEMMs through ``torch.matmul``, ``torch.topk`` selections, padded lists.
 
+``dtype=torch.bfloat16`` keeps the table (and the IVF index's list-ordered copy) in bf16 and
+searches it in place with the bf16 kernels: half the memory, no fp32 copy at any point, a GPU
+bf16 tensor of ``infer()`` is adopted as it is.  Queries are rounded to bf16; distances are
+those of fp32 arithmetic on the bf16 values.  k-means and the centroids stay fp32.  A bf16
+index has no torch composition: off the GPU (or past ``k = 128``) it runs the ops' twin.
+
 CLI (same flags as the reference)::
 
     python -m euler_amd.tools.knn --embedding_file embedding_0.npy --id_file ids_0.npy \
-        [--query_file q.csv] [--index_type ivfflat|flat] [--k 10] [--out result.npz]
+        [--query_file q.csv] [--index_type ivfflat|flat] [--k 10] [--out result.npz] [--dtype fp32|bf16]
 
 ``--embedding_file`` / ``--id_file`` also take comma-separated lists of equal length (the
 per-rank files of a multi-rank ``infer()``), concatenated in order.
@@ -56,14 +62,48 @@ def _kernels(use_kernels, device):
     return use_kernels is not False and torch.device(device).type == "cuda"
 
 
+_ROWS = 1 << 16  # rows of a bf16 table that exist in fp32 at a time (conversion, assignment)
+
+
+def _table_dtype(dtype, use_kernels):
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("dtype must be torch.float32 or torch.bfloat16, got %r" % (dtype,))
+    if dtype == torch.bfloat16 and use_kernels is False:
+        raise ValueError("a bfloat16 index has no torch composition (use_kernels=False)")
+    return dtype
+
+
+def _bf16_table(x, device):
+    """``x`` as a contiguous bf16 tensor on ``device``: a tensor that already is one is returned
+    as it is, anything else is converted ``_ROWS`` rows at a time"""
+    if isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16:
+        return x.to(device).contiguous()
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=device)
+    for r0 in range(0, x.shape[0], _ROWS):
+        out[r0:r0 + _ROWS] = torch.as_tensor(x[r0:r0 + _ROWS], dtype=torch.float32).to(device)
+    return out
+
+
+def _queries(q, dtype, device):
+    """fp32 queries on the device; for a bf16 index rounded to bf16 first"""
+    q = torch.as_tensor(q, device=device)
+    return q.to(torch.bfloat16).float() if dtype == torch.bfloat16 else q.to(torch.float32)
+
+
 class FlatIndex:
-    def __init__(self, d, device=None, chunk=8192, use_kernels=None):
+    def __init__(self, d, device=None, chunk=8192, use_kernels=None, dtype=torch.float32):
         self.d, self.device, self.chunk = d, _dev(device), chunk
+        self.dtype = _table_dtype(dtype, use_kernels)
         self.use_kernels = _kernels(use_kernels, self.device)
-        self.xb = torch.zeros(0, d, device=self.device)
+        self.xb = torch.zeros(0, d, device=self.device, dtype=self.dtype)
         self.xn = torch.zeros(0, device=self.device)
 
     def add(self, x):
+        if self.dtype == torch.bfloat16:
+            x = _bf16_table(x, self.device)
+            self.xb = x if self.ntotal == 0 else torch.cat([self.xb, x])
+            self.xn = knn_ops.row_norms(self.xb)
+            return
         x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
         self.xb = torch.cat([self.xb, x])
         self.xn = (self.xb * self.xb).sum(1)
@@ -73,11 +113,11 @@ class FlatIndex:
         return self.xb.shape[0]
 
     def search(self, q, k):
-        q = torch.as_tensor(q, dtype=torch.float32, device=self.device)
+        q = _queries(q, self.dtype, self.device)
         k = min(int(k), self.ntotal)
         ds, ids = [], []
         for s in range(0, q.shape[0], self.chunk):
-            if self.use_kernels and 1 <= k <= knn_ops.MAX_KERNEL_K:
+            if self.dtype == torch.bfloat16 or (self.use_kernels and 1 <= k <= knn_ops.MAX_KERNEL_K):
                 # query chunks only bound the partial lists; no [chunk, ntotal] matrix
                 v, i = knn_ops.flat_topk(q[s:s + self.chunk], self.xb, k, xn=self.xn)
                 ds.append(v)
@@ -115,9 +155,11 @@ def kmeans(x, ncent, iters=20, seed=0, min_points_per_centroid=4, use_kernels=No
 
 
 class IVFFlatIndex:
-    def __init__(self, d, ncent, nprobe=10, device=None, min_points_per_centroid=4, iters=20, use_kernels=None):
+    def __init__(self, d, ncent, nprobe=10, device=None, min_points_per_centroid=4, iters=20, use_kernels=None,
+                 dtype=torch.float32):
         self.d, self.ncent, self.nprobe = d, int(ncent), int(nprobe)
         self.device = _dev(device)
+        self.dtype = _table_dtype(dtype, use_kernels)
         self.use_kernels = _kernels(use_kernels, self.device)
         self.min_pts, self.iters = min_points_per_centroid, iters
         self.cent = None
@@ -126,18 +168,27 @@ class IVFFlatIndex:
         self.ntrain = 0
 
     def train(self, x):
-        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+        """k-means in fp32 on the sample ``x`` (for a bf16 index too: the centroids stay fp32)"""
+        x = torch.as_tensor(x, device=self.device).to(torch.float32)
         self.ntrain = x.shape[0]
         self.cent = kmeans(x, self.ncent, self.iters, min_points_per_centroid=self.min_pts,
                            use_kernels=self.use_kernels)
         self.ncent = self.cent.shape[0]
 
     def add(self, x):
-        x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
-        self.xb = x if self.xb is None else torch.cat([self.xb, x])
-        self.assign = _assign(self.xb, self.cent, self.use_kernels)
-        self.xn = (self.xb * self.xb).sum(1)
-        if self.use_kernels:
+        if self.dtype == torch.bfloat16:
+            x = _bf16_table(x, self.device)
+            self.xb = x if self.xb is None else torch.cat([self.xb, x])
+            # the rows are the queries of `nearest` against the small fp32 centroid set
+            self.assign = torch.cat([_assign(self.xb[r0:r0 + _ROWS].float(), self.cent, self.use_kernels)
+                                     for r0 in range(0, self.xb.shape[0], _ROWS)])
+            self.xn = knn_ops.row_norms(self.xb)
+        else:
+            x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+            self.xb = x if self.xb is None else torch.cat([self.xb, x])
+            self.assign = _assign(self.xb, self.cent, self.use_kernels)
+            self.xn = (self.xb * self.xb).sum(1)
+        if self.use_kernels or self.dtype == torch.bfloat16:
             # CSR inverted lists: the database in list order, original order kept inside a list
             self.list_ptr, self.row_of = knn_ops.build_lists(self.assign, self.ncent)
             self.xs, self.xns = self.xb[self.row_of], self.xn[self.row_of]
@@ -163,10 +214,11 @@ class IVFFlatIndex:
         return 0 if self.xb is None else self.xb.shape[0]
 
     def search(self, q, k, chunk=1024):
-        q = torch.as_tensor(q, dtype=torch.float32, device=self.device)
+        q = _queries(q, self.dtype, self.device)
         nprobe = min(self.nprobe, self.ncent)
         ds, ids = [], []
         fused = self.use_kernels and 1 <= int(k) <= knn_ops.MAX_KERNEL_K and nprobe <= 64
+        fused = fused or self.dtype == torch.bfloat16  # the ops' twin serves what the kernels do not
         if not fused and self.lists is None:
             self._pad_lists()
         for s in range(0, q.shape[0], chunk):
@@ -194,15 +246,17 @@ class IVFFlatIndex:
         return torch.cat(ds).cpu().numpy(), torch.cat(ids).cpu().numpy()
 
 
-def build_index(embedding, index_type="ivfflat", device=None, use_kernels=None, max_points_per_centroid=None):
+def build_index(embedding, index_type="ivfflat", device=None, use_kernels=None, max_points_per_centroid=None,
+                dtype=torch.float32):
     """``max_points_per_centroid`` caps the k-means training set at that many points per
-    centroid (a seeded random subset; faiss uses 256); None trains on everything."""
+    centroid (a seeded random subset; faiss uses 256); None trains on everything (in fp32, for
+    a bf16 index too).  ``dtype``: the table's storage, ``torch.float32`` or ``torch.bfloat16``."""
     n, d = embedding.shape
     if index_type == "flat":
-        idx = FlatIndex(d, device, use_kernels=use_kernels)
+        idx = FlatIndex(d, device, use_kernels=use_kernels, dtype=dtype)
     elif index_type == "ivfflat":
         ncent = int(4 * math.sqrt(n))
-        idx = IVFFlatIndex(d, ncent, nprobe=10, device=device, use_kernels=use_kernels)
+        idx = IVFFlatIndex(d, ncent, nprobe=10, device=device, use_kernels=use_kernels, dtype=dtype)
         train = embedding
         if max_points_per_centroid is not None and n > int(max_points_per_centroid) * max(ncent, 1):
             g = torch.Generator(device="cpu").manual_seed(1234)
@@ -224,6 +278,8 @@ def main(argv=None):
     p.add_argument("--k", type=int, default=10)
     p.add_argument("--out", default="result.npz")
     p.add_argument("--device", default=None)
+    p.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
+                   help="storage of the table: bf16 halves the memory and searches with the bf16 kernels")
     p.add_argument("--max_points_per_centroid", type=int, default=None,
                    help="cap on the k-means training set per centroid (faiss uses 256; default: no cap)")
     a = p.parse_args(argv)
@@ -236,7 +292,8 @@ def main(argv=None):
     else:
         ids = np.arange(len(emb))
     assert len(ids) == len(emb), "ids and embeddings differ in length"
-    index = build_index(emb, a.index_type, a.device, max_points_per_centroid=a.max_points_per_centroid)
+    index = build_index(emb, a.index_type, a.device, max_points_per_centroid=a.max_points_per_centroid,
+                        dtype=torch.bfloat16 if a.dtype == "bf16" else torch.float32)
     query = np.loadtxt(a.query_file, dtype=np.float32, delimiter=",", ndmin=2) if a.query_file else emb[:25]
     D, I = index.search(query, a.k)
     res_ids = np.where(I >= 0, ids[np.clip(I, 0, None)], -1)
