@@ -13,64 +13,12 @@
 // Both map one row b to a group of lanes (4 fp32 / 8 bf16 columns per lane) like gat.hip,
 // so a wave covers several short rows and the row reductions are group shuffles.
 #include "hip/common.h"
+#include "hip/kg_dev.h"
 #include "hip/launchers.h"
 
 #include <hipcub/hipcub.hpp>
 
 namespace euler_hip {
-
-template <typename T>
-struct EV;
-template <>
-struct EV<bf16_t> {
-  static constexpr int N = 8;
-  __device__ __forceinline__ static void load(const bf16_t* p, float* f) {
-    const uint4_t u = *reinterpret_cast<const uint4_t*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(u[i] << 16);
-      f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-    }
-  }
-  __device__ __forceinline__ static void store(bf16_t* p, const float* f) {
-    *reinterpret_cast<uint4_t*>(p) = pack_bf16x8(f);
-  }
-};
-template <>
-struct EV<float> {
-  static constexpr int N = 4;
-  __device__ __forceinline__ static void load(const float* p, float* f) {
-    const float4_t u = *reinterpret_cast<const float4_t*>(p);
-    f[0] = u[0];
-    f[1] = u[1];
-    f[2] = u[2];
-    f[3] = u[3];
-  }
-  __device__ __forceinline__ static void store(float* p, const float* f) {
-    *reinterpret_cast<float4_t*>(p) = float4_t{f[0], f[1], f[2], f[3]};
-  }
-};
-
-// sum over aligned groups of g lanes; all lanes of a group follow the same path
-__device__ __forceinline__ float emb_group_sum(float v, int g) {
-  for (int o = g >> 1; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-struct RowLane {
-  int64_t row;
-  int sub;
-  bool ok;
-};
-__device__ __forceinline__ RowLane row_lane(int lp, int64_t rows) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
-  RowLane r;
-  r.row = wave * (64 / lp) + lane / lp;
-  r.sub = lane & (lp - 1);
-  r.ok = r.row < rows;
-  return r;
-}
 
 // numerically stable sigmoid cross-entropy with logits
 __device__ __forceinline__ float sigmoid_ce(float x, float y) {
@@ -516,43 +464,6 @@ struct KgArgs {
   int K, D, kind, corrupt, normalize, lp;
 };
 
-__device__ __forceinline__ void kg_load_norm(const float* tab, int64_t row, int sub, int D, int lp, bool normalize,
-                                             float* x, float& nrm) {
-  float part = 0.f;
-#pragma unroll
-  for (int v = 0; v < 4; ++v) x[v] = 0.f;
-  if (sub * 4 < D && row >= 0) {
-    EV<float>::load(tab + row * D + sub * 4, x);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) part += x[v] * x[v];
-  }
-  nrm = 1.f;
-  if (normalize) {
-    nrm = fmaxf(sqrtf(emb_group_sum(part, lp)), 1e-12f);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) x[v] /= nrm;
-  }
-}
-
-// this lane's part of a score; the caller reduces over the group
-__device__ __forceinline__ float kg_part(int kind, const float* h, const float* r, const float* t) {
-  float p = 0.f;
-#pragma unroll
-  for (int v = 0; v < 4; ++v) {
-    if (kind == 2) {
-      p += h[v] * r[v] * t[v];
-    } else {
-      const float d = h[v] + r[v] - t[v];
-      p += kind == 0 ? fabsf(d) : d * d;
-    }
-  }
-  return p;
-}
-
-__device__ __forceinline__ float kg_finish(int kind, float s) {
-  return kind == 0 ? -s : (kind == 1 ? -sqrtf(s) : s);
-}
-
 __global__ __launch_bounds__(256) void kg_fwd_kernel(KgArgs a, float* __restrict__ pos_score,
                                                      float* __restrict__ neg_score) {
   const RowLane L = row_lane(a.lp, a.B);
@@ -607,29 +518,6 @@ __device__ __forceinline__ void kg_grad(int kind, int lp, float g, const float* 
       dr[v] += gd;
       dt[v] -= gd;
     }
-  }
-}
-
-// push the gradient w.r.t. a normalised row through x / |x| and add it to the table grad
-// (occ: store it as occurrence row ``row`` instead — summed per table row afterwards by a
-// segment reduction, no atomics on hot rows)
-__device__ __forceinline__ void kg_scatter(float* __restrict__ dtab, int64_t row, int sub, int D, int lp,
-                                           bool normalize, const float* xhat, float nrm, float* dx, bool occ = false) {
-  if (normalize) {
-    float p = 0.f;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) p += xhat[v] * dx[v];
-    const float dot = emb_group_sum(p, lp);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) dx[v] = (dx[v] - xhat[v] * dot) / nrm;
-  }
-  if (sub * 4 < D && row >= 0) {
-    if (occ) {
-      EV<float>::store(dtab + row * D + sub * 4, dx);
-      return;
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) atomicAdd(dtab + row * D + sub * 4 + v, dx[v]);
   }
 }
 
@@ -918,17 +806,6 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
     w[1] = pack_bf16x2(v[2], v[3]);
     reinterpret_cast<tl2u*>(out)[i] = w;
   });
-}
-
-inline int row_lanes(int chunks) {
-  int lp = 1;
-  while (lp < chunks && lp < 64) lp <<= 1;
-  return lp;
-}
-inline dim3 row_grid(int64_t rows, int lp) {
-  const int64_t rpw = 64 / lp;
-  const int64_t waves = (rows + rpw - 1) / rpw;
-  return dim3(static_cast<uint32_t>((waves + 3) / 4));
 }
 
 __global__ __launch_bounds__(256) void gather_f32_bf16_kernel(const float* __restrict__ x, int64_t n_rows, int D,

@@ -306,6 +306,21 @@ hipError_t eh_kg_rank_scan(const float* Q, const float* C, const int64_t* true_i
                            const int64_t* filt_ptr, const int32_t* filt_idx, int64_t nf, int64_t B, int64_t N, int d,
                            int kind, int S, int64_t* better, int64_t* ties, hipStream_t s);
 
+// kg_proj.hip (TransH / TransD scores with the projection inside the score kernel).  model 0 =
+// TransH (proj_r = hyper [Nr, D], proj_e unused), 1 = TransD (proj_e = entity_transfer [Ne, D],
+// proj_r = relation_transfer [Nr, D]); kind 0 = l1, 1 = l2; corrupt 0 front, 1 tail, 2 both (front
+// scores first).  fp32 tables of n_ent / n_rel rows, D % 4 == 0, D <= 256; an id outside its table
+// addresses the table's last row (Embedding's padding row), in the kernel.  The backward
+// reads the forward's scores and adds into the four table gradients by fp32 atomics.
+hipError_t eh_kgp_fwd(int model, const float* ent, const float* rel, const float* proj_e, const float* proj_r,
+                      int64_t n_ent, int64_t n_rel, const int64_t* src, const int64_t* dst, const int64_t* ridx,
+                      const int64_t* neg, int64_t B, int K, int D, int kind, int corrupt, float* pos_score, float* neg_score, hipStream_t s);
+hipError_t eh_kgp_bwd(int model, const float* ent, const float* rel, const float* proj_e, const float* proj_r,
+                      int64_t n_ent, int64_t n_rel, const int64_t* src, const int64_t* dst, const int64_t* ridx,
+                      const int64_t* neg, int64_t B, int K, int D, int kind, int corrupt, const float* pos_score, const float* neg_score,
+                      const float* gpos, const float* gneg, float* dent, float* drel, float* dproj_e, float* dproj_r,
+                      hipStream_t s);
+
 // graph_build.hip (DeviceGraph.from_edges: edge list -> per-(row, type) CSR).  Keys are
 // ((row * T + type) << dst_bits) | dst_row, at most 63 bits; payloads are edge indices (the
 // reverse copy of edge i under `symmetric` is E + i); status int64 [4]: [0] failure bits

@@ -13,6 +13,8 @@ can pick node_src / edge / node_dst embeddings.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -96,15 +98,22 @@ class TransX(nn.Module):
         ``rows``: a row-sparse step (RowSparseKGTrainer) passes its gathered entity rows
         (``{"entity_encoder": [n, D], "entity_transfer": ...}``) and src / dst / neg are
         POSITIONS into them; the fused kinds then score and differentiate straight on those
-        rows (the kg_fwd / kg_bwd kernels, the row gradients land on the gathered rows)."""
+        rows (the kg_fwd / kg_bwd kernels, or kgp_fwd / kgp_bwd for the projected TransH /
+        TransD; the row gradients land on the gathered rows)."""
         if self._fused_ok(src.device, rows):
             ent, rtab = self.entity_encoder, self.relation_encoder
-            if rows is not None:
-                table, s, d, n = rows["entity_encoder"], src, dst, neg
+            if self.proj_model is not None:
+                # raw ids / positions: the kernels apply Embedding._rows (out of range = last row)
+                table = rows["entity_encoder"] if rows is not None else ent.weight
+                pos_s, neg_s = gnn_ops.kg_score_proj(self.proj_model, table, rtab.weight, self._proj_tables(rows),
+                                                     src, dst, rel, neg, self.fused_kind, self.corrupt)
             else:
-                table, s, d, n = ent.weight, ent._rows(src), ent._rows(dst), ent._rows(neg)
-            pos_s, neg_s = gnn_ops.kg_score(table, rtab.weight, s, d, rtab._rows(rel), n, self.fused_kind,
-                                            self.corrupt, True)
+                if rows is not None:
+                    table, s, d, n = rows["entity_encoder"], src, dst, neg
+                else:
+                    table, s, d, n = ent.weight, ent._rows(src), ent._rows(dst), ent._rows(neg)
+                pos_s, neg_s = gnn_ops.kg_score(table, rtab.weight, s, d, rtab._rows(rel), n, self.fused_kind,
+                                                self.corrupt, True)
             pos, neg_s = pos_s.view(-1, 1, 1), neg_s.view(pos_s.shape[0], 1, -1)
         else:
             pos, neg_s = self.energy_scores(*self.generate_embedding(src, dst, neg, rel, rows=rows))
@@ -169,15 +178,32 @@ class TransX(nn.Module):
 
     # score kind of the fused gfx950 kernel (embed.hip kg_fwd / kg_bwd), None = unfused
     fused_kind = None
+    # "transh" / "transd": the fused kernels are kg_proj.hip kgp_fwd / kgp_bwd, which project
+    # every entity row inside the score kernel (gnn_ops.kg_score_proj over _proj_tables)
+    proj_model = None
+
+    def _set_proj_fused(self):
+        """fused_kind of a projected subclass; ``EULER_AMD_KG_PROJ_FUSED=0`` (read per model, so
+        one process can build both variants) keeps the torch composition"""
+        if os.environ.get("EULER_AMD_KG_PROJ_FUSED", "1") != "0":
+            self.fused_kind = "l1" if self.l1 else "l2"
+
+    def _proj_tables(self, rows=None):
+        """the projection tables of gnn_ops.kg_score_proj (``rows``: the gathered ones)"""
+        raise NotImplementedError
+
+    def _fused_embeddings(self, src, dst, rel):
+        """(src, rel, dst) rows as the unfused forward returns them"""
+        ent = self.entity_encoder
+        return self.norm_emb(ent(src)), self.norm_emb(self.relation_encoder(rel)), self.norm_emb(ent(dst))
 
     def _fused_forward(self, src, dst, neg, rel):
         """gather + l2-normalise + score of the positive and every corrupted triple, and
         the whole backward into the two tables, in two kernels."""
-        ent, rtab = self.entity_encoder, self.relation_encoder
         loss, pos, neg_s = self.loss_scores(src, dst, neg, rel)
         metric = self.metric(pos.detach().float().cpu(), neg_s.detach().float().cpu())
         with torch.no_grad():
-            s, d, r = self.norm_emb(ent(src)), self.norm_emb(ent(dst)), self.norm_emb(rtab(rel))
+            s, r, d = self._fused_embeddings(src, dst, rel)
         return [s.reshape(-1, s.shape[-1]), r.reshape(-1, r.shape[-1]), d.reshape(-1, d.shape[-1])], loss, \
             self.metric_name, metric
 
@@ -201,8 +227,8 @@ class TransE(TransX):
         if ent_dim != rel_dim:
             raise ValueError("Entity dim and Relation dim should be equal in TransE")
         self.margin = margin
-        # subclasses with projections (TransH / TransD) override generate_embedding and
-        # keep the unfused path
+        # subclasses with projections (TransH / TransD) override generate_embedding and set
+        # their own fused kind (_set_proj_fused)
         if type(self).generate_embedding is TransE.generate_embedding:
             self.fused_kind = "l1" if l1 else "l2"
 
@@ -219,6 +245,17 @@ class TransH(TransE):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.hyper_vector = Embedding(self.edge_max_id + 1, self.ent_dim)
+        self._set_proj_fused()
+
+    proj_model = "transh"
+
+    def _proj_tables(self, rows=None):
+        return (self.hyper_vector.weight,)
+
+    def _fused_embeddings(self, src, dst, rel):
+        e, hyper = self.entity_encoder, self.hyper_vector(rel)
+        return (self.projection(e(src), hyper), self.norm_emb(self.relation_encoder(rel)),
+                self.projection(e(dst), hyper))
 
     @staticmethod
     def projection(x, hyper):
@@ -267,6 +304,18 @@ class TransD(TransE):
         super().__init__(*args, **kwargs)
         self.entity_transfer = Embedding(self.node_max_id + 1, self.ent_dim)
         self.relation_transfer = Embedding(self.edge_max_id + 1, self.rel_dim)
+        self._set_proj_fused()
+
+    proj_model = "transd"
+
+    def _proj_tables(self, rows=None):
+        ent_t = rows["entity_transfer"] if rows is not None else self.entity_transfer.weight
+        return (ent_t, self.relation_transfer.weight)
+
+    def _fused_embeddings(self, src, dst, rel):
+        e, et, rt = self.entity_encoder, self.entity_transfer, self.relation_transfer(rel)
+        return (self.projection(e(src), et(src), rt), self.norm_emb(self.relation_encoder(rel)),
+                self.projection(e(dst), et(dst), rt))
 
     @staticmethod
     def projection(x, ent_t, rel_t):

@@ -12,6 +12,9 @@ op                     replaces (reference)                        kernel
                        (mp_utils/base.py:80-91)
 ``kg_score``           4 lookups + 4 l2-normalise + TransE/         ``embed.hip`` kg_fwd / kg_bwd
                        DistMult score (transX.py:72-145)
+``kg_score_proj``      the same with TransH's hyperplane /          ``kg_proj.hip`` kgp_fwd / kgp_bwd
+                       TransD's transfer-vector projection of
+                       every entity row (transH.py, transD.py)
 ``unique_first``       tf.unique (first-occurrence order)           ``unique.hip`` (hash table)
 =====================  ==========================================  =================================
 
@@ -30,6 +33,7 @@ from euler_amd.ops.mp_ops import SegmentIndex
 
 __all__ = ["EdgeCSR", "gat_aggregate", "gat_aggregate_reference", "RelationTiles", "relation_transform",
            "relation_transform_reference", "sgns_loss", "sgns_loss_reference", "kg_score", "kg_score_reference",
+           "kg_score_proj", "kg_score_proj_reference", "KG_PROJ_MODELS",
            "unique_first", "unique_first_padded", "KG_KINDS", "KG_CORRUPT", "sgns_fwd_idx", "occ_csr", "sgns_grad", "tall_linear", "xent",
            "splitk_mm_t", "splitk_linear"]
 
@@ -950,6 +954,107 @@ def kg_score(ent, rel, src, dst, ridx, neg, kind="l1", corrupt="both", normalize
                               ids(neg, ent.shape[0]).view(B, -1), KG_KINDS[kind], KG_CORRUPT[corrupt],
                               bool(normalize))
     return kg_score_reference(ent, rel, src, dst, ridx, neg, kind, corrupt, normalize)
+
+
+# ----------------------------------------------------------------------------- K10 projected KG scores
+KG_PROJ_MODELS = {"transh": 0, "transd": 1}
+
+
+def kg_score_proj_reference(model, ent, rel, proj, src, dst, ridx, neg, kind="l1", corrupt="both"):
+    """the torch composition of :func:`kg_score_proj` (TransH.projection / TransD.projection and
+    generate_embedding of models/knowledge_graph.py)"""
+    B = src.numel()
+
+    def ids(t, tab, *shape):  # Embedding._rows: an id outside the table is its last row
+        t, n_rows = t.reshape(*shape).long(), tab.shape[0]
+        return torch.where((t < 0) | (t >= n_rows), torch.full_like(t, n_rows - 1), t)
+
+    s, d, ri, n = ids(src, ent, -1), ids(dst, ent, -1), ids(ridx, rel, -1), ids(neg, ent, B, -1)
+    r = F.normalize(rel[ri], dim=-1)
+    if KG_PROJ_MODELS[model] == 0:
+        (hyper,) = proj
+        w = F.normalize(hyper[ri], dim=-1)
+
+        def row(i, q):
+            x = ent[i]
+            return x - (x * q).sum(-1, keepdim=True) * q
+    else:
+        ent_t, rel_t = proj
+        w = rel_t[ri]
+
+        def row(i, q):
+            x = ent[i]
+            return F.normalize(x + (x * ent_t[i]).sum(-1, keepdim=True) * q, dim=-1)
+
+    h, t, nn_ = row(s, w), row(d, w), row(n, w.unsqueeze(1))
+
+    def score(a, b, c):
+        e = a + b - c
+        return -(e.abs().sum(-1) if kind == "l1" else e.norm(dim=-1))
+
+    pos = score(h, r, t)
+    r1, h1, t1 = r.unsqueeze(1), h.unsqueeze(1), t.unsqueeze(1)
+    if corrupt == "front":
+        ns = score(nn_, r1, t1)
+    elif corrupt == "tail":
+        ns = score(h1, r1, nn_)
+    else:
+        ns = torch.cat([score(nn_, r1, t1), score(h1, r1, nn_)], -1)
+    return pos, ns
+
+
+class _KgScoreProj(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, kind, corrupt, src, dst, ridx, neg, ent, rel, proj_r, proj_e):
+        pos_s, neg_s = hip().kg_proj.fwd(model, ent, rel, proj_e, proj_r, src, dst, ridx, neg, kind, corrupt)
+        ctx.save_for_backward(ent, rel, proj_r, src, dst, ridx, neg, pos_s, neg_s,
+                              *(() if proj_e is None else (proj_e,)))
+        ctx.args = (model, kind, corrupt)
+        return pos_s, neg_s
+
+    @staticmethod
+    def backward(ctx, gpos, gneg):
+        ent, rel, proj_r, src, dst, ridx, neg, pos_s, neg_s, *pe = ctx.saved_tensors
+        proj_e = pe[0] if pe else None
+        model, kind, corrupt = ctx.args
+        gpos = torch.zeros_like(pos_s) if gpos is None else gpos.float().contiguous()
+        gneg = torch.zeros_like(neg_s) if gneg is None else gneg.float().contiguous()
+        dent, drel, dproj_r = torch.zeros_like(ent), torch.zeros_like(rel), torch.zeros_like(proj_r)
+        dproj_e = None if proj_e is None else torch.zeros_like(proj_e)
+        hip().kg_proj.bwd(model, ent, rel, proj_e, proj_r, src, dst, ridx, neg, kind, corrupt, pos_s, neg_s, gpos,
+                          gneg, dent, drel, dproj_e, dproj_r)
+        return None, None, None, None, None, None, None, dent, drel, dproj_r, dproj_e
+
+
+def kg_score_proj(model, ent, rel, proj, src, dst, ridx, neg, kind="l1", corrupt="both"):
+    """Scores of the positive triples ``(src, ridx, dst)`` [B] and of the corrupted ones [B, K]
+    (front or tail) or [B, 2K] (both: front scores first) of the projected translation models,
+    with every row gathered from its table and projected inside the score kernel (kg_proj.hip).
+
+    ``model="transh"``, ``proj=(hyper,)`` [Nr, D]: ``P(x) = x - (w . x) w`` with ``w`` the
+    l2-normalised hyper row, entity rows not normalised; ``model="transd"``, ``proj=(ent_t,
+    rel_t)`` [Ne, D], [Nr, D]: ``x_perp = normalize(x + (x . ent_t[x]) rel_t[r])``.  Score
+    ``-|h' + normalize(r) - t'|`` in ``l1`` or ``l2``.  Differentiable in every table.  An id
+    outside its table addresses the table's last row (``Embedding._rows``; the kernels do this
+    themselves, so no clamping pass runs in front of them).  CPU
+    tensors, non-fp32 tables and D % 4 != 0 or D > 256 take :func:`kg_score_proj_reference`."""
+    m = KG_PROJ_MODELS[model]
+    proj = tuple(proj)
+    if len(proj) != (1 if m == 0 else 2):
+        raise ValueError("kg_score_proj: proj is (hyper,) for transh and (ent_t, rel_t) for transd")
+    if kind not in ("l1", "l2"):
+        raise ValueError("kg_score_proj: kind must be 'l1' or 'l2', got %r" % (kind,))
+    tables = (ent, rel) + proj
+    B, D = src.numel(), ent.shape[1]
+    if use_hip(*tables) and all(t.dtype == torch.float32 for t in tables) and D % 4 == 0 and 0 < D <= 256:
+        def ids(t):
+            return t.reshape(-1).long().contiguous()
+
+        proj_e, proj_r = (None, proj[0]) if m == 0 else proj
+        return _KgScoreProj.apply(m, KG_KINDS[kind], KG_CORRUPT[corrupt], ids(src), ids(dst), ids(ridx),
+                                  ids(neg).view(B, -1), ent.contiguous(), rel.contiguous(), proj_r.contiguous(),
+                                  None if proj_e is None else proj_e.contiguous())
+    return kg_score_proj_reference(model, ent, rel, proj, src, dst, ridx, neg, kind, corrupt)
 
 
 # ----------------------------------------------------------------------------- K8 unique
