@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""TransH / TransD training throughput under ``EdgeEstimator(device_graph=True)``: the fused
-projected score kernels (csrc/hip/kg_proj.hip kgp_fwd / kgp_bwd) against the torch composition
-of the same model (``EULER_AMD_KG_PROJ_FUSED=0``), alternating in one process.
+"""TransH / TransD / TransR training throughput under ``EdgeEstimator(device_graph=True)``: the
+fused projected score kernels (csrc/hip/kg_proj.hip kgp_fwd / kgp_bwd; ``--models transr``:
+csrc/hip/kg_transr.hip kgr_fwd / kgr_bwd) against the torch composition of the same model
+(``EULER_AMD_KG_PROJ_FUSED=0``), alternating in one process.
 
 The run is ``benchmarks/bench_gcn.py --model M --dataset fb15k`` (the README's TransE estimator
 row: batch 512, 5 negatives, dim 32) with the device path only and a longer window: the rate
@@ -9,7 +10,7 @@ is the estimator's own over the last log interval (a quarter of ``--steps``), wh
 device synchronise.  Prints one JSON line: per model and route the rates of every repetition,
 their median, and the median time per step.
 
-    python benchmarks/bench_kg_proj.py [--models transh,transd] [--routes fused,torch] [--reps 3]
+    python benchmarks/bench_kg_proj.py [--models transh,transd] [--routes fused,torch] [--reps 3] [--dim 32]
 """
 import argparse
 import json
@@ -28,7 +29,7 @@ from benchmarks import bench_gcn  # noqa: E402
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--models", default="transh,transd")
-    ap.add_argument("--routes", default="fused,torch", help="fused: kg_proj.hip; torch: EULER_AMD_KG_PROJ_FUSED=0")
+    ap.add_argument("--routes", default="fused,torch", help="fused: kg_proj.hip / kg_transr.hip; torch: EULER_AMD_KG_PROJ_FUSED=0")
     ap.add_argument("--reps", type=int, default=3, help="repetitions of every (model, route), routes alternating")
     ap.add_argument("--steps", type=int, default=4000)
     ap.add_argument("--batch-size", dest="batch_size", type=int, default=512)

@@ -547,6 +547,8 @@ PYBIND11_MODULE(_hip_ops, m) {
   register_knn_bf16_ops(kb);
   auto kp = m.def_submodule("kg_proj");
   register_kg_proj_ops(kp);
+  auto kr = m.def_submodule("kg_transr");
+  register_kg_transr_ops(kr);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

@@ -55,6 +55,9 @@ void register_knn_bf16_ops(py::module& m);
 // binding_kg_proj.cpp: TransH / TransD scores with the projection inside the score kernel,
 // kg_proj.hip (registered on the submodule _hip_ops.kg_proj)
 void register_kg_proj_ops(py::module& m);
+// binding_kg_transr.cpp: TransR scores with the MFMA projection inside the score kernel,
+// kg_transr.hip (registered on the submodule _hip_ops.kg_transr)
+void register_kg_transr_ops(py::module& m);
 
 namespace euler_bind {
 

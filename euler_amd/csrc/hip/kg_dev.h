@@ -1,6 +1,7 @@
 // Device helpers shared by the row-group kernels of embed.hip (sgns_*, kg_fwd / kg_bwd, kg_step) and
 // kg_proj.hip (kgp_fwd / kgp_bwd): one row per group of lp lanes, 4 fp32 / 8 bf16 columns per
-// lane, row reductions as xor butterflies inside the group.  One copy, included by both.
+// lane, row reductions as xor butterflies inside the group.  One copy, included by both, and by
+// kg_transr.hip (kgr_fwd / kgr_bwd) for the score conventions and the group reductions.
 #pragma once
 
 #include "hip/common.h"
@@ -59,6 +60,11 @@ __device__ __forceinline__ RowLane row_lane(int lp, int64_t rows) {
   r.ok = r.row < rows;
   return r;
 }
+
+// kg_proj.hip, kg_transr.hip: an id outside its table addresses the table's last row
+// (utils/layers.py Embedding._rows: the padding row), so the caller needs no clamping pass and no
+// id can leave the table
+__device__ __forceinline__ int64_t kgp_row(int64_t id, int64_t n) { return id < 0 || id >= n ? n - 1 : id; }
 
 // this lane's 4 columns of table row `row` (zeros outside the width or for row < 0), divided by
 // the row's l2 norm (clamped at 1e-12) when `normalize`; nrm = that norm, 1 otherwise

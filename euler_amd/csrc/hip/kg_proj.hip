@@ -47,10 +47,6 @@ struct KgpArgs {
   int K, D, kind, corrupt, lp;
 };
 
-// an id outside its table addresses the table's last row (utils/layers.py Embedding._rows: the
-// padding row), so the caller needs no clamping pass and no id can leave the table
-__device__ __forceinline__ int64_t kgp_row(int64_t id, int64_t n) { return id < 0 || id >= n ? n - 1 : id; }
-
 // one entity row through the projection: x its raw columns, xp its transfer row (TransD),
 // s = w . x (TransH) or x . x_p (TransD), y the projected row, ny = |x + s r_p| (TransD; else 1)
 struct KgpRow {

@@ -321,6 +321,19 @@ hipError_t eh_kgp_bwd(int model, const float* ent, const float* rel, const float
                       const float* gpos, const float* gneg, float* dent, float* drel, float* dproj_e, float* dproj_r,
                       hipStream_t s);
 
+// kg_transr.hip (TransR scores, the per-triple projection x M_r on fp32 MFMA inside the score
+// kernel: one block per triple).  ent [n_ent, E], rel [n_rel, R], mat [n_rel, E * R] (each row a
+// row-major [E, R] matrix), fp32 and 16-byte aligned; E % 4 == 0, R % 4 == 0, 4 <= E, R <= 128,
+// K <= 14; kind / corrupt / ids as kgp_fwd.  The backward reads the forward's scores and adds
+// into the three table gradients by fp32 atomics.
+hipError_t eh_kgr_fwd(const float* ent, const float* rel, const float* mat, int64_t n_ent, int64_t n_rel,
+                      const int64_t* src, const int64_t* dst, const int64_t* ridx, const int64_t* neg, int64_t B, int K,
+                      int E, int R, int kind, int corrupt, float* pos_score, float* neg_score, hipStream_t s);
+hipError_t eh_kgr_bwd(const float* ent, const float* rel, const float* mat, int64_t n_ent, int64_t n_rel,
+                      const int64_t* src, const int64_t* dst, const int64_t* ridx, const int64_t* neg, int64_t B, int K,
+                      int E, int R, int kind, int corrupt, const float* pos_score, const float* neg_score,
+                      const float* gpos, const float* gneg, float* dent, float* drel, float* dmat, hipStream_t s);
+
 // graph_build.hip (DeviceGraph.from_edges: edge list -> per-(row, type) CSR).  Keys are
 // ((row * T + type) << dst_bits) | dst_row, at most 63 bits; payloads are edge indices (the
 // reverse copy of edge i under `symmetric` is E + i); status int64 [4]: [0] failure bits

@@ -16,7 +16,7 @@ device-only:
   ``node_type`` (the reference ``sample_node``); draws are the ``alias_sample`` kernel on
   Philox streams (seed, counter, stream) — stream 1 triples, stream 2 corruptions;
 * the model's own ``loss_scores`` (the fused ``kg_score`` kernels for TransE / DistMult,
-  ``kg_score_proj`` for TransH / TransD, the torch composition for TransR), the metric
+  ``kg_score_proj`` for TransH / TransD / TransR), the metric
   (MRR / MR / hit@10 of the
   positive among its corruptions) accumulated on the device;
 * one flat optimizer launch over every table and parameter (``models/captured.py``),
@@ -163,9 +163,9 @@ class RowSparseKGTrainer(KGTrainer):
 
     The model scores the step on the gathered rows: the trainer passes them with src /
     dst / corruption POSITIONS into them (``loss_scores(..., rows=)``), so TransE /
-    DistMult run the fused kg_fwd / kg_bwd kernels (TransH / TransD: kgp_fwd / kgp_bwd)
-    straight on the gathered rows and the row gradients come out per gathered row, ready
-    for the owners' update; TransR runs its torch composition on the same rows.
+    DistMult run the fused kg_fwd / kg_bwd kernels (TransH / TransD: kgp_fwd / kgp_bwd,
+    TransR: kgr_fwd / kgr_bwd) straight on the gathered rows and the row gradients come out
+    per gathered row, ready for the owners' update.
 
     Table ownership: row ``r`` lives on rank ``r % world`` (ShardedEmbedding's layout), so
     a ``sharded=True`` model's shard — or any model's table on one rank — IS the trainer's

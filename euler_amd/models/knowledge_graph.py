@@ -99,7 +99,7 @@ class TransX(nn.Module):
         (``{"entity_encoder": [n, D], "entity_transfer": ...}``) and src / dst / neg are
         POSITIONS into them; the fused kinds then score and differentiate straight on those
         rows (the kg_fwd / kg_bwd kernels, or kgp_fwd / kgp_bwd for the projected TransH /
-        TransD; the row gradients land on the gathered rows)."""
+        TransD and kgr_fwd / kgr_bwd for TransR; the row gradients land on the gathered rows)."""
         if self._fused_ok(src.device, rows):
             ent, rtab = self.entity_encoder, self.relation_encoder
             if self.proj_model is not None:
@@ -178,8 +178,9 @@ class TransX(nn.Module):
 
     # score kind of the fused gfx950 kernel (embed.hip kg_fwd / kg_bwd), None = unfused
     fused_kind = None
-    # "transh" / "transd": the fused kernels are kg_proj.hip kgp_fwd / kgp_bwd, which project
-    # every entity row inside the score kernel (gnn_ops.kg_score_proj over _proj_tables)
+    # "transh" / "transd": the fused kernels are kg_proj.hip kgp_fwd / kgp_bwd, "transr":
+    # kg_transr.hip kgr_fwd / kgr_bwd; they project every entity row inside the score kernel
+    # (gnn_ops.kg_score_proj over _proj_tables)
     proj_model = None
 
     def _set_proj_fused(self):
@@ -281,6 +282,21 @@ class TransR(TransX):
                          metric_name, corrupt, sharded)
         self.margin = margin
         self.transfer_matrix = Embedding(edge_max_id + 1, ent_dim * rel_dim)
+        # dimensions the kernels do not cover keep the torch composition
+        if gnn_ops.kg_transr_dims_ok(ent_dim, rel_dim):
+            self._set_proj_fused()
+
+    proj_model = "transr"
+
+    def _proj_tables(self, rows=None):
+        # relation-indexed: never one of the row-sparse trainer's gathered tables
+        return (self.transfer_matrix.weight,)
+
+    def _fused_embeddings(self, src, dst, rel):
+        e = self.entity_encoder
+        mat = self.transfer_matrix(rel).reshape(-1, self.ent_dim, self.rel_dim)
+        return (self.projection(e(src), mat), self.norm_emb(self.relation_encoder(rel)),
+                self.projection(e(dst), mat))
 
     def projection(self, x, mat):
         # x [B, k, ent] @ mat [B, ent, rel] -> one batched GEMM per batch (rocBLAS strided batched)

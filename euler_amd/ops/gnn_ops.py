@@ -15,6 +15,8 @@ op                     replaces (reference)                        kernel
 ``kg_score_proj``      the same with TransH's hyperplane /          ``kg_proj.hip`` kgp_fwd / kgp_bwd
                        TransD's transfer-vector projection of
                        every entity row (transH.py, transD.py)
+                       or TransR's per-relation matrix product      ``kg_transr.hip`` kgr_fwd / kgr_bwd
+                       (transR.py: gather [B, E, R] + 3 bmm)
 ``unique_first``       tf.unique (first-occurrence order)           ``unique.hip`` (hash table)
 =====================  ==========================================  =================================
 
@@ -33,7 +35,7 @@ from euler_amd.ops.mp_ops import SegmentIndex
 
 __all__ = ["EdgeCSR", "gat_aggregate", "gat_aggregate_reference", "RelationTiles", "relation_transform",
            "relation_transform_reference", "sgns_loss", "sgns_loss_reference", "kg_score", "kg_score_reference",
-           "kg_score_proj", "kg_score_proj_reference", "KG_PROJ_MODELS",
+           "kg_score_proj", "kg_score_proj_reference", "KG_PROJ_MODELS", "kg_transr_dims_ok",
            "unique_first", "unique_first_padded", "KG_KINDS", "KG_CORRUPT", "sgns_fwd_idx", "occ_csr", "sgns_grad", "tall_linear", "xent",
            "splitk_mm_t", "splitk_linear"]
 
@@ -957,12 +959,13 @@ def kg_score(ent, rel, src, dst, ridx, neg, kind="l1", corrupt="both", normalize
 
 
 # ----------------------------------------------------------------------------- K10 projected KG scores
-KG_PROJ_MODELS = {"transh": 0, "transd": 1}
+KG_PROJ_MODELS = {"transh": 0, "transd": 1, "transr": 2}
+KG_TRANSR_MAX_DIM, KG_TRANSR_MAX_NEGS = 128, 14  # limits of kg_transr.hip: LDS tile of M_r, 16-row MFMA tile
 
 
 def kg_score_proj_reference(model, ent, rel, proj, src, dst, ridx, neg, kind="l1", corrupt="both"):
-    """the torch composition of :func:`kg_score_proj` (TransH.projection / TransD.projection and
-    generate_embedding of models/knowledge_graph.py)"""
+    """the torch composition of :func:`kg_score_proj` (TransH.projection / TransR.projection /
+    TransD.projection and generate_embedding of models/knowledge_graph.py)"""
     B = src.numel()
 
     def ids(t, tab, *shape):  # Embedding._rows: an id outside the table is its last row
@@ -978,6 +981,13 @@ def kg_score_proj_reference(model, ent, rel, proj, src, dst, ridx, neg, kind="l1
         def row(i, q):
             x = ent[i]
             return x - (x * q).sum(-1, keepdim=True) * q
+    elif KG_PROJ_MODELS[model] == 2:
+        (mat,) = proj
+        w = mat[ri].reshape(B, ent.shape[1], rel.shape[1])
+
+        def row(i, q):  # q [B, E, R]: one bmm over each triple's i.numel() / B rows (TransR.projection)
+            x = ent[i].reshape(B, i.numel() // max(B, 1), ent.shape[1])
+            return F.normalize(torch.bmm(x, q), dim=-1).reshape(*i.shape, rel.shape[1])
     else:
         ent_t, rel_t = proj
         w = rel_t[ri]
@@ -986,7 +996,7 @@ def kg_score_proj_reference(model, ent, rel, proj, src, dst, ridx, neg, kind="l1
             x = ent[i]
             return F.normalize(x + (x * ent_t[i]).sum(-1, keepdim=True) * q, dim=-1)
 
-    h, t, nn_ = row(s, w), row(d, w), row(n, w.unsqueeze(1))
+    h, t, nn_ = row(s, w), row(d, w), row(n, w if KG_PROJ_MODELS[model] == 2 else w.unsqueeze(1))
 
     def score(a, b, c):
         e = a + b - c
@@ -1026,6 +1036,29 @@ class _KgScoreProj(torch.autograd.Function):
         return None, None, None, None, None, None, None, dent, drel, dproj_r, dproj_e
 
 
+class _KgScoreTransR(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kind, corrupt, src, dst, ridx, neg, ent, rel, mat):
+        pos_s, neg_s = hip().kg_transr.fwd(ent, rel, mat, src, dst, ridx, neg, kind, corrupt)
+        ctx.save_for_backward(ent, rel, mat, src, dst, ridx, neg, pos_s, neg_s)
+        ctx.args = (kind, corrupt)
+        return pos_s, neg_s
+
+    @staticmethod
+    def backward(ctx, gpos, gneg):
+        ent, rel, mat, src, dst, ridx, neg, pos_s, neg_s = ctx.saved_tensors
+        gpos = torch.zeros_like(pos_s) if gpos is None else gpos.float().contiguous()
+        gneg = torch.zeros_like(neg_s) if gneg is None else gneg.float().contiguous()
+        dent, drel, dmat = torch.zeros_like(ent), torch.zeros_like(rel), torch.zeros_like(mat)
+        hip().kg_transr.bwd(ent, rel, mat, src, dst, ridx, neg, *ctx.args, pos_s, neg_s, gpos, gneg, dent, drel, dmat)
+        return None, None, None, None, None, None, dent, drel, dmat
+
+
+def kg_transr_dims_ok(E, R):
+    """dimensions the TransR kernels (kg_transr.hip) cover"""
+    return E % 4 == 0 and R % 4 == 0 and 4 <= E <= KG_TRANSR_MAX_DIM and 4 <= R <= KG_TRANSR_MAX_DIM
+
+
 def kg_score_proj(model, ent, rel, proj, src, dst, ridx, neg, kind="l1", corrupt="both"):
     """Scores of the positive triples ``(src, ridx, dst)`` [B] and of the corrupted ones [B, K]
     (front or tail) or [B, 2K] (both: front scores first) of the projected translation models,
@@ -1037,15 +1070,34 @@ def kg_score_proj(model, ent, rel, proj, src, dst, ridx, neg, kind="l1", corrupt
     ``-|h' + normalize(r) - t'|`` in ``l1`` or ``l2``.  Differentiable in every table.  An id
     outside its table addresses the table's last row (``Embedding._rows``; the kernels do this
     themselves, so no clamping pass runs in front of them).  CPU
-    tensors, non-fp32 tables and D % 4 != 0 or D > 256 take :func:`kg_score_proj_reference`."""
+    tensors, non-fp32 tables and D % 4 != 0 or D > 256 take :func:`kg_score_proj_reference`.
+
+    ``model="transr"``, ``proj=(mat,)`` [Nr, E * R], each row a row-major [E, R] matrix, ``ent``
+    [Ne, E], ``rel`` [Nr, R] (E != R allowed): ``P(x) = normalize(x M_r)`` of the raw entity row,
+    one block per triple with the products on fp32 MFMA (kg_transr.hip).  The kernels cover fp32
+    GPU tables (16-byte aligned) with E % 4 == 0, R % 4 == 0, 4 <= E, R <= 128 and at most 14
+    negatives per triple; everything else takes :func:`kg_score_proj_reference`."""
     m = KG_PROJ_MODELS[model]
     proj = tuple(proj)
-    if len(proj) != (1 if m == 0 else 2):
+    if m == 2 and len(proj) != 1:
+        raise ValueError("kg_score_proj: proj is (mat,) for transr")
+    if len(proj) != (2 if m == 1 else 1):
         raise ValueError("kg_score_proj: proj is (hyper,) for transh and (ent_t, rel_t) for transd")
     if kind not in ("l1", "l2"):
         raise ValueError("kg_score_proj: kind must be 'l1' or 'l2', got %r" % (kind,))
     tables = (ent, rel) + proj
     B, D = src.numel(), ent.shape[1]
+    if m == 2:
+        K = neg.numel() // B if B else 0
+        if (use_hip(*tables) and all(t.dtype == torch.float32 for t in tables)
+                and kg_transr_dims_ok(D, rel.shape[1]) and K <= KG_TRANSR_MAX_NEGS
+                and tuple(proj[0].shape) == (rel.shape[0], D * rel.shape[1])):
+            tabs = [t.contiguous() for t in tables]
+            if all(t.data_ptr() % 16 == 0 for t in tabs):
+                return _KgScoreTransR.apply(KG_KINDS[kind], KG_CORRUPT[corrupt], *(
+                    t.reshape(-1).long().contiguous() for t in (src, dst, ridx)),
+                    neg.reshape(-1).long().contiguous().view(B, K), *tabs)
+        return kg_score_proj_reference(model, ent, rel, proj, src, dst, ridx, neg, kind, corrupt)
     if use_hip(*tables) and all(t.dtype == torch.float32 for t in tables) and D % 4 == 0 and 0 < D <= 256:
         def ids(t):
             return t.reshape(-1).long().contiguous()
