@@ -14,12 +14,22 @@ For each score kind (``l1``: TransE, ``l2``: TransE(l1=False), ``dot``: DistMult
 * for ``l1`` / ``l2`` the composition the kernel replaces, ``dataset.synthetic.tail_ranks``
   (tail side, raw; a [chunk, N] ``torch.cdist`` matrix per chunk), imported unchanged.
 
+``--models transh,transd,transr`` measures the projected models instead: ``rank_triples`` on both
+sides, filtered, on the fused route (``kg_rank_ops.rank_counts_proj``: the projection inside the
+scan kernel) and on the per-relation loop it replaces (``EULER_AMD_KG_RANK_PROJ_FUSED=0``),
+alternating in one process, ``--repeat`` passes each after a warm-up pass of each route.  The test
+relations are drawn with Zipf frequencies (``p(r) ~ 1 / (r + 1)``): a few relations hold thousands
+of queries, most a handful, as in FB15k's test split.  TransR runs at ``--dim`` and at
+``--transr-dim`` (entity and relation dimension alike).  Reports medians and ranges, the share of
+equal ranks between the routes and the number of single-relation query tiles with their mean fill.
+
 Each figure is the median of ``--repeat`` passes after a warm-up pass, with
 ``torch.cuda.synchronize`` around the timed region; peak bytes are what a pass allocates over
 what was allocated before it.  Prints one JSON line.
 
     python benchmarks/bench_kg_rank.py [--entities 14951] [--relations 1345] [--dim 100]
         [--triples 59071] [--batch 4096] [--repeat 3] [--kinds l1 l2 dot]
+        [--models transh,transd,transr] [--transr-dim 32]
 """
 import argparse
 import json
@@ -49,6 +59,62 @@ def _timed(fn, repeat, torch):
     return statistics.median(times) * 1e3, [round(t * 1e3, 3) for t in times], int(peak), out
 
 
+def _ab(model, triples, known, batch, repeat, torch, kg_eval):
+    """fused route and per-relation loop, alternating; ms per pass"""
+    def run(fused):
+        os.environ["EULER_AMD_KG_RANK_PROJ_FUSED"] = "1" if fused else "0"
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = kg_eval.rank_triples(model, *triples, known=known, batch=batch)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, out
+        finally:
+            os.environ.pop("EULER_AMD_KG_RANK_PROJ_FUSED", None)
+
+    ranks = {f: run(f)[1] for f in (True, False)}  # warm-up of both routes
+    ms = {True: [], False: []}
+    for _ in range(repeat):
+        for f in (True, False):
+            ms[f].append(run(f)[0])
+    same = torch.cat([ranks[True][s] == ranks[False][s] for s in ("head", "tail")]).double().mean()
+    diff = max(int((ranks[True][s] - ranks[False][s]).abs().max()) for s in ("head", "tail"))
+
+    def stats(v):
+        return {"ms": round(statistics.median(v), 3), "ms_min": round(min(v), 3), "ms_max": round(max(v), 3),
+                "ms_all": [round(t, 3) for t in v]}
+
+    return {"fused": stats(ms[True]), "per_relation_loop": stats(ms[False]),
+            "speedup": round(statistics.median(ms[False]) / statistics.median(ms[True]), 2),
+            "ranks_equal_fraction": round(float(same), 6), "max_rank_difference": diff}
+
+
+def _bench_models(a, torch, res, dev, gen):
+    from euler_amd import models as Z
+    from euler_amd.models import kg_eval
+
+    n, N, R = a.triples, a.entities, a.relations
+    src = torch.randint(0, N, (n,), generator=gen, device=dev)
+    dst = torch.randint(0, N, (n,), generator=gen, device=dev)
+    freq = 1.0 / torch.arange(1, R + 1, device=dev, dtype=torch.float64)
+    rel = torch.multinomial(freq, n, replacement=True, generator=gen)
+    known = kg_eval.KnownTriples(src, rel, dst, N, device=dev)
+    tiles = fill = 0
+    for s0 in range(0, n, a.batch):  # the single-relation query tiles of every batch
+        cnt = torch.unique(rel[s0:s0 + a.batch], return_counts=True)[1]
+        tiles += int(((cnt + 63) // 64).sum())
+        fill += int(cnt.sum())
+    res.update(relation_frequencies="zipf", distinct_test_relations=int(torch.unique(rel).numel()),
+               query_tiles_per_side=tiles, mean_tile_fill=round(fill / tiles / 64, 4), models={})
+    for name in a.models.split(","):
+        for dim in ([a.dim, a.transr_dim] if name == "transr" else [a.dim]):
+            torch.manual_seed(a.seed)
+            cls = {"transh": Z.TransH, "transd": Z.TransD, "transr": Z.TransR}[name]
+            model = cls(-1, [0], N - 1, R - 1, dim, dim).to(dev)
+            res["models"]["%s_d%d" % (name, dim)] = _ab(model, (src, rel, dst), known, a.batch, a.repeat, torch,
+                                                         kg_eval)
+
+
 def main(argv=None):
     import torch
 
@@ -62,6 +128,8 @@ def main(argv=None):
     ap.add_argument("--kinds", nargs="+", default=["l1", "l2", "dot"], choices=["l1", "l2", "dot"])
     ap.add_argument("--filter-alpha", dest="alpha", type=float, default=1.2)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--models", default="", help="transh,transd,transr: the projected models, fused route vs loop")
+    ap.add_argument("--transr-dim", dest="transr_dim", type=int, default=32)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_kg_rank measures on a GPU; none is available")
@@ -71,6 +139,13 @@ def main(argv=None):
 
     dev = torch.device("cuda")
     gen = torch.Generator(device=dev).manual_seed(a.seed)
+    if a.models:
+        res = {"bench": "kg_rank_proj", "entities": a.entities, "relations": a.relations, "dim": a.dim,
+               "triples": a.triples, "batch": a.batch, "repeat": a.repeat, "sides": "head + tail, filtered",
+               "device": torch.cuda.get_device_name(0)}
+        _bench_models(a, torch, res, dev, gen)
+        print(json.dumps(res))
+        return res
     n, N, R = a.triples, a.entities, a.relations
     src = torch.randint(0, N, (n,), generator=gen, device=dev)
     rel = torch.randint(0, R, (n,), generator=gen, device=dev)

@@ -549,6 +549,8 @@ PYBIND11_MODULE(_hip_ops, m) {
   register_kg_proj_ops(kp);
   auto kr = m.def_submodule("kg_transr");
   register_kg_transr_ops(kr);
+  auto krp = m.def_submodule("kg_rank_proj");
+  register_kg_rank_proj_ops(krp);
   register_gnn_ops(m);
   register_tree_ops(m);
   register_gcn_ops(m);

@@ -58,6 +58,9 @@ void register_kg_proj_ops(py::module& m);
 // binding_kg_transr.cpp: TransR scores with the MFMA projection inside the score kernel,
 // kg_transr.hip (registered on the submodule _hip_ops.kg_transr)
 void register_kg_transr_ops(py::module& m);
+// binding_kg_rank_proj.cpp: rank counts of TransH / TransD / TransR with the candidates projected
+// inside the scan kernel, kg_rank_proj.hip (registered on the submodule _hip_ops.kg_rank_proj)
+void register_kg_rank_proj_ops(py::module& m);
 
 namespace euler_bind {
 

@@ -28,7 +28,9 @@
 //                  16 lanes of a query are reduced with shuffles and lane tx = 0 stores the
 //                  (query, split) partial.  Every partial has exactly one writer, so the result
 //                  is deterministic.
+// kg_term, kg_filtered and the pair epilogue live in kg_rank_dev.h, shared with kg_rank_proj.hip.
 #include "hip/common.h"
+#include "hip/kg_rank_dev.h"
 #include "hip/launchers.h"
 
 #include <limits.h>
@@ -46,17 +48,6 @@ constexpr int kKgrLd = kKgrKC + 4;  // staging row stride (floats): 16-byte alig
 constexpr int kKgrMaxSplits = 4096;
 constexpr int kKgrNLoad = (kKgrTQ + kKgrTC) * kKgrKC / kKgrThreads;  // staged floats per thread and chunk
 
-// one term of the score, folded into the accumulator (the only place a score is computed)
-template <int KIND>
-__device__ __forceinline__ float kg_term(float acc, float q, float c) {
-  if (KIND == 0) return __fadd_rn(acc, fabsf(__fsub_rn(q, c)));
-  if (KIND == 1) {
-    const float t = __fsub_rn(q, c);
-    return fmaf(t, t, acc);
-  }
-  return fmaf(q, c, acc);
-}
-
 template <int KIND>
 __global__ __launch_bounds__(kKgrThreads) void kg_rank_true_kernel(const float* __restrict__ Q,
                                                                    const float* __restrict__ C,
@@ -73,21 +64,6 @@ __global__ __launch_bounds__(kKgrThreads) void kg_rank_true_kernel(const float* 
     }
     ts[b] = acc;
   });
-}
-
-// is e in the ascending list idx[lo, hi)
-__device__ __forceinline__ bool kg_filtered(const int32_t* __restrict__ idx, int64_t lo, int64_t hi, int32_t e) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    const int32_t v = idx[mid];
-    if (v == e) return true;
-    if (v < e) {
-      lo = mid + 1;
-    } else {
-      hi = mid;
-    }
-  }
-  return false;
 }
 
 template <int KIND, bool VEC>
@@ -223,18 +199,7 @@ __global__ __launch_bounds__(kKgrThreads) void kg_rank_scan_kernel(
         for (int j = 0; j < 4; ++j) {
           const int64_t e = c0 + tx + 16 * j;
           if (b >= B || e >= N || e == tru[i]) continue;
-          const float sv = acc[i][j];
-          const bool bt = KIND == 2 ? sv > tsc[i] : sv < tsc[i];
-          const bool tie = sv == tsc[i];
-          if (!(bt || tie)) continue;
-          if (filt_ptr != nullptr) {
-            int64_t lo = filt_ptr[b], hi = filt_ptr[b + 1];
-            if (lo < 0) lo = 0;
-            if (hi > nf) hi = nf;
-            if (kg_filtered(filt_idx, lo, hi, static_cast<int32_t>(e))) continue;
-          }
-          nb[i] += bt ? 1 : 0;
-          nt[i] += tie ? 1 : 0;
+          kg_rank_pair<KIND>(acc[i][j], tsc[i], b, e, filt_ptr, filt_idx, nf, nb[i], nt[i]);
         }
       }
     }

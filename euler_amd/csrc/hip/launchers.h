@@ -306,6 +306,22 @@ hipError_t eh_kg_rank_scan(const float* Q, const float* C, const int64_t* true_i
                            const int64_t* filt_ptr, const int32_t* filt_idx, int64_t nf, int64_t B, int64_t N, int d,
                            int kind, int S, int64_t* better, int64_t* ties, hipStream_t s);
 
+// kg_rank_proj.hip (rank counts of the projected models: the candidates are projected under the
+// query tile's relation inside the kernel).  model 0 TransH (pr = hyper [n_rel, E]), 1 TransD (pe =
+// entity_transfer [N, E], pr = relation_transfer [n_rel, E]), 2 TransR (pr = mat [n_rel, E * R]);
+// ent [N, E], rel [n_rel, R] (E == R unless model 2), fp32 and 16-byte aligned, E % 4 == 0,
+// R % 4 == 0, 4 <= E, R <= eh_kg_rank_proj_max_dim().  given / true_idx [B] in [0, N); order [B]:
+// the queries sorted by relation; tiles [T, 3] int32: relation row, first sorted position and
+// count (1..64) of every run of queries of one relation.  side 0 = head (query P(given) - rho),
+// 1 = tail (P(given) + rho); kind 0 = l1, 1 = squared l2.  Launches the true-score pass (ts [B])
+// and the scan; better / ties [B, S] and the filter as eh_kg_rank_scan.
+int eh_kg_rank_proj_max_dim();
+hipError_t eh_kg_rank_proj(int model, const float* ent, const float* rel, const float* pe, const float* pr, int64_t N,
+                           int E, int R, const int64_t* given, const int64_t* true_idx, const int64_t* order,
+                           const int32_t* tiles, int64_t T, int64_t B, int side, int kind, const int64_t* filt_ptr,
+                           const int32_t* filt_idx, int64_t nf, int S, float* ts, int64_t* better, int64_t* ties,
+                           hipStream_t s);
+
 // kg_proj.hip (TransH / TransD scores with the projection inside the score kernel).  model 0 =
 // TransH (proj_r = hyper [Nr, D], proj_e unused), 1 = TransD (proj_e = entity_transfer [Ne, D],
 // proj_r = relation_transfer [Nr, D]); kind 0 = l1, 1 = l2; corrupt 0 front, 1 tail, 2 both (front

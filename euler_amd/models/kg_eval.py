@@ -20,6 +20,8 @@ rule of ``dataset.synthetic.tail_ranks``), ``1 + better`` ("optimistic") or
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from euler_amd.ops import kg_rank_ops
@@ -132,8 +134,12 @@ def rank_triples(model, src, rel, dst, known=None, sides=SIDES, ties="pessimisti
     among (it must contain every true entity), e.g. the hubs of a typed KG; default all
     entities 0..node_max_id.
 
-    For relation-dependent models (TransH / TransR / TransD) the triples are grouped by
-    relation and ``entity_space(r)`` is built once per relation."""
+    The relation-dependent models (TransH / TransR / TransD) rank through
+    ``kg_rank_ops.rank_counts_proj``: one call per (batch, side) on the raw tables, the
+    candidates projected inside the kernel under each query's relation, no ``entity_space``.
+    With ``cands``, with tables the op does not cover (``rank_proj_covered``) or with
+    ``EULER_AMD_KG_RANK_PROJ_FUSED=0`` (read per call) the triples are grouped by relation and
+    ``entity_space(r)`` is built once per relation instead."""
     if ties not in TIE_RULES:
         raise ValueError("ties must be one of %s, got %r" % (TIE_RULES, ties))
     sides = tuple(sides)
@@ -189,16 +195,38 @@ def rank_triples(model, src, rel, dst, known=None, sides=SIDES, ties="pessimisti
                 better, tie = kg_rank_ops.rank_counts(q, table, true_pos.contiguous(), kind, ptr, idx)
                 out[s][ix] = _ranks(better, tie, ties)
 
+    def run_proj(table, rel_table, proj):
+        """the fused route of the projected models: raw tables, any mix of relations per call"""
+        rows = model.relation_encoder._rows(rel)
+        for a in range(0, n, batch):
+            h, r, t, rr = src[a:a + batch], rel[a:a + batch], dst[a:a + batch], rows[a:a + batch].contiguous()
+            for s in sides:
+                given, true = (h, t) if s == "tail" else (t, h)
+                ptr, idx = known.filter(s, h, r, t) if known is not None else (None, None)
+                better, tie = kg_rank_ops.rank_counts_proj(model.proj_model, table, rel_table, proj,
+                                                           given.contiguous(), true.contiguous(), rr, s, kind,
+                                                           ptr, idx)
+                out[s][a:a + batch] = _ranks(better, tie, ties)
+
     if not model.relation_dependent:
         run(model.entity_space(), model.relation_row, torch.arange(n, device=dev))
-    else:
-        order = torch.argsort(rel, stable=True)
-        rels, counts = torch.unique_consecutive(rel[order], return_counts=True)
-        start = 0
-        for r, c in zip(rels.tolist(), counts.tolist()):
-            rho = model.relation_row(r)
-            run(model.entity_space(r), lambda _r, rho=rho: rho, order[start:start + c])
-            start += c
+        return out
+    if (getattr(model, "proj_model", None) is not None and cands is None
+            and os.environ.get("EULER_AMD_KG_RANK_PROJ_FUSED", "1") != "0"):
+        table, rel_table = model._rank_table().detach(), model.relation_encoder.weight.detach()
+        proj = tuple(p.detach() for p in model._proj_tables())
+        if model.proj_model == "transd":  # entity_transfer is indexed like the entity table
+            proj = (proj[0][:num_ent], proj[1])
+        if kg_rank_ops.rank_proj_covered(model.proj_model, table, rel_table, proj):
+            run_proj(table, rel_table, proj)
+            return out
+    order = torch.argsort(rel, stable=True)
+    rels, counts = torch.unique_consecutive(rel[order], return_counts=True)
+    start = 0
+    for r, c in zip(rels.tolist(), counts.tolist()):
+        rho = model.relation_row(r)
+        run(model.entity_space(r), lambda _r, rho=rho: rho, order[start:start + c])
+        start += c
     return out
 
 
