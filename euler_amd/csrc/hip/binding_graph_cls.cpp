@@ -5,8 +5,11 @@
 // out the step kernel's LDS, owns the slab / partial buffers, and step() only launches
 // (hipGraph-capturable: no allocation, no host sync) on torch's current stream: gc_step, then
 // gc_reduce into the flat gradient or — set_optimizer() on one process — into the flat
-// optimizer's update.
+// optimizer's update.  infer() scores an explicit request list with the forward-only pack kernel
+// (graph_cls_infer.hip) over the same static tensors and parameter views: it is not a per-step
+// method (it packs the requests on the host and uploads the pack table), so it is not captured.
 #include <algorithm>
+#include <cstdlib>
 
 #include "hip/binding_util.h"
 #include "hip/graph_cls_args.h"
@@ -143,6 +146,18 @@ class GraphClsPlan : private PlanDict {
     a.ostep_inc = nullptr;
     if (has("max_lds")) max_lds_ = geti("max_lds");
     layout(dmax);
+    // the forward-only kernel: every graph's node count on the host (the packs), its own LDS map
+    {
+      torch::Tensor rec_h = rec.cpu();
+      const int32_t* rh = rec_h.data_ptr<int32_t>();
+      counts_.resize(a.G);
+      for (int64_t g = 0; g < a.G; ++g) {
+        counts_[g] = rh[g * kGcRec];
+        TORCH_CHECK_VALUE(counts_[g] >= 0 && counts_[g] <= a.nmax, "GraphClsPlan: graph ", g, " has ", counts_[g],
+                          " nodes, nmax is ", a.nmax);
+      }
+    }
+    infer_layout(dmax);
     // reduce
     GcReduceArgs& r = r_;
     r.slab = a.slab;
@@ -211,6 +226,60 @@ class GraphClsPlan : private PlanDict {
     launch_ok(eh_gc_reduce(&r_, cur_stream()), "gc_reduce");
     return prof;
   }
+  // logits [n][C] and pooled embeddings [n][E] of the graphs gidx (int32, host or the plan's
+  // device; any order, repeats allowed), in request order, with the current parameter values.
+  // Consecutive requests are packed greedily: a pack closes at R rows or kGcPackGraphs graphs
+  // (EULER_AMD_GRAPH_INFER_PACK=k: at k graphs; 1 gives one graph per block).
+  void infer(torch::Tensor gidx, torch::Tensor logits, torch::Tensor emb) {
+    TORCH_CHECK(gidx.scalar_type() == torch::kInt32 && gidx.dim() == 1 && gidx.is_contiguous(),
+                "GraphClsPlan.infer: 'gidx' must be a contiguous 1-D int32 tensor");
+    TORCH_CHECK(!gidx.is_cuda() || gidx.device() == device(), "GraphClsPlan.infer: 'gidx' is on ", gidx.device(),
+                ", the plan is on ", device());
+    const int64_t n = gidx.numel();
+    TORCH_CHECK(n <= INT32_MAX / std::max(ia_.E, ia_.C), "GraphClsPlan.infer: too many requests");
+    need(logits, torch::kFloat32, n * ia_.C, "logits_out");
+    need(emb, torch::kFloat32, n * ia_.E, "emb_out");
+    infer_packs_ = 0;
+    if (n == 0) return;
+    torch::Tensor gh = gidx.cpu();
+    const int32_t* g = gh.data_ptr<int32_t>();
+    int cap = kGcPackGraphs;
+    if (const char* e = std::getenv("EULER_AMD_GRAPH_INFER_PACK")) {
+      const int k = std::atoi(e);
+      if (k >= 1) cap = std::min(k, kGcPackGraphs);
+    }
+    // requests, then the pack table: one upload
+    std::vector<int32_t> up(g, g + n);
+    int64_t npacks = 0;
+    for (int64_t q = 0; q < n;) {
+      int32_t rec[kGcPackRec] = {static_cast<int32_t>(q), 0};
+      int32_t rows = 0;
+      while (q < n && rec[1] < cap) {
+        TORCH_CHECK(g[q] >= 0 && g[q] < ia_.G, "GraphClsPlan.infer: graph index ", g[q], " outside [0, ", ia_.G, ")");
+        const int32_t c = counts_[g[q]];
+        if (rec[1] > 0 && rows + c > ia_.R) break;
+        rec[2 + rec[1]++] = rows;
+        rows += c;
+        ++q;
+      }
+      up.insert(up.end(), rec, rec + kGcPackRec);
+      ++npacks;
+    }
+    const c10::DeviceGuard guard(device());
+    torch::Tensor dev = torch::from_blob(up.data(), {static_cast<int64_t>(up.size())}, torch::kInt32).to(device());
+    GcInferArgs a = ia_;
+    a.n = static_cast<int32_t>(n);
+    a.npacks = static_cast<int32_t>(npacks);
+    a.gidx = dev.data_ptr<int32_t>();
+    a.pack = a.gidx + n;
+    a.logits = logits.data_ptr<float>();
+    a.emb = emb.data_ptr<float>();
+    launch_ok(eh_gc_infer(&a, cur_stream()), "gc_infer");
+    infer_packs_ = npacks;
+  }
+  int64_t infer_packs() const { return infer_packs_; }
+  int64_t infer_rows() const { return ia_.R; }
+  int64_t infer_lds_bytes() const { return ia_.lds_bytes; }
   torch::Tensor gidx() const { return gidx_; }
   int64_t lds_bytes() const { return a_.lds_bytes; }
   bool z_kept() const { return a_.zst != 0; }
@@ -218,6 +287,9 @@ class GraphClsPlan : private PlanDict {
  private:
   GcStepArgs a_{};
   GcReduceArgs r_{}, ro_{};
+  GcInferArgs ia_{};
+  std::vector<int32_t> counts_;  // nodes of every graph (host copy of the records' first column)
+  int64_t infer_packs_ = 0;      // packs of the last infer() call
   std::vector<torch::Tensor> keep_, opt_keep_;
   torch::Tensor slab_, loss_part_, acc_part_, gidx_;
   int64_t max_lds_ = 160 * 1024;  // "max_lds" in the dict: a smaller budget (tests of the global-weight path)
@@ -258,6 +330,70 @@ class GraphClsPlan : private PlanDict {
     if (a.zst) off += (a.L - 1) * ((z1 + 15) / 16 * 16);
     a.lds_bytes = static_cast<int32_t>(off);
   }
+
+  // the forward-only kernel's arguments and LDS map: R = the largest of 64 / 48 / 32 / 16 rows
+  // that holds the largest graph and fits the budget
+  void infer_layout(int64_t dmax) {
+    const GcStepArgs& s = a_;
+    GcInferArgs& a = ia_;
+    a.L = s.L;
+    a.kind = s.kind;
+    a.self_loops = s.self_loops;
+    a.E = s.E;
+    a.C = s.C;
+    a.nadj = s.nadj;
+    a.G = s.G;
+    a.rec = s.rec;
+    a.fpair = s.fpair;
+    a.fw = s.fw;
+    a.table = s.table;
+    a.tab_rows = s.tab_rows;
+    a.Wfc = s.Wfc;
+    a.bfc = s.bfc;
+    a.Wout = s.Wout;
+    for (int l = 0; l <= s.L; ++l) a.D[l] = s.D[l];
+    for (int l = 0; l < s.L; ++l) {
+      a.adj_of[l] = s.adj_of[l];
+      a.W[l] = s.W[l];
+      a.Wf[l] = s.Wf[l];
+      a.bl[l] = s.bl[l];
+      a.eps[l] = s.eps[l];
+    }
+    for (int j = 0; j < s.nadj; ++j) a.adj[j] = s.adj[j];
+    const int64_t kmax = s.kind == 1 ? 2 * dmax : dmax;
+    a.ldx = static_cast<int32_t>(dmax + 4);
+    a.ldz = static_cast<int32_t>(kmax + 4);
+    a.trp = s.trp;
+    a.ldsm = s.ldsm;
+    a.ldt = s.ldt;
+    a.ldpe = (s.E + 15) / 16 * 16 + 4;
+    const int64_t budget = 160 * 1024 - kGcInferStaticLds;
+    int64_t off = 0;
+    for (int64_t R = kGcMaxRows; R >= 16; R -= 16) {
+      off = 0;
+      auto take = [&](int64_t bytes) {
+        const int64_t o = off;
+        off += (bytes + 15) / 16 * 16;
+        return static_cast<int32_t>(o);
+      };
+      a.R = static_cast<int32_t>(R);
+      a.lda = static_cast<int32_t>(R + 4);
+      a.lds_x[0] = take(R * a.ldx * 4);
+      a.lds_x[1] = take(R * a.ldx * 4);
+      a.lds_z = take(R * a.ldz * 4);
+      a.lds_a = take(a.nadj * R * a.lda * 4);
+      a.lds_invc = take(a.nadj * R * 4);
+      a.lds_s = take(R * a.ldsm * 4);
+      a.lds_t = take(static_cast<int64_t>(a.trp) * a.ldt * 4);
+      a.lds_p = take(static_cast<int64_t>(kGcPackGraphs) * a.lda * 4);
+      a.lds_px = take(static_cast<int64_t>(kGcPackGraphs) * a.ldx * 4);
+      a.lds_pe = take(static_cast<int64_t>(kGcPackGraphs) * a.ldpe * 4);
+      a.lds_bytes = static_cast<int32_t>(off);
+      if (R < s.nmax || off <= budget) break;
+    }
+    TORCH_CHECK_VALUE(a.R >= s.nmax && off <= budget, "GraphClsPlan: the forward-only kernel needs ", off,
+                      " bytes of LDS for ", a.R, " rows (> ", budget, ")");
+  }
 };
 
 }  // namespace
@@ -268,6 +404,10 @@ void register_graph_cls_ops(py::module& m) {
       .def("step", &GraphClsPlan::step, py::arg("fused_opt") = false)
       .def("set_optimizer", &GraphClsPlan::set_optimizer)
       .def("gidx", &GraphClsPlan::gidx)
+      .def("infer", &GraphClsPlan::infer, py::arg("gidx"), py::arg("logits_out"), py::arg("emb_out"))
+      .def_property_readonly("infer_packs", &GraphClsPlan::infer_packs)
+      .def_property_readonly("infer_rows", &GraphClsPlan::infer_rows)
+      .def_property_readonly("infer_lds_bytes", &GraphClsPlan::infer_lds_bytes)
       .def("profile", &GraphClsPlan::profile)
       .def_property_readonly("lds_bytes", &GraphClsPlan::lds_bytes)
       .def_property_readonly("z_kept", &GraphClsPlan::z_kept);

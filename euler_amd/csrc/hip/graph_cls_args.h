@@ -120,9 +120,56 @@ struct GcReduceArgs {
   float lr, b1, b2, eps, wd, grad_scale;
 };
 
+// Forward-only scoring of an explicit request list (graph_cls_infer.hip): one launch, one
+// block per *pack*.  A pack is a run of consecutive requests whose node counts sum to at
+// most R rows (at most kGcPackGraphs graphs); graph q of the pack owns the LDS rows
+// [r0_q, r0_q + n_q), so the per-mask adjacency is one block-diagonal A [R][R], the row
+// tiles of every GEMM are full, and the pooled head is three GEMMs over the pack's graphs
+// (P X_L, fc, out_fc) with the membership matrix P [16][R].  The host builds the packs
+// (greedy, request order) and uploads the requests and the pack table with every call.
+constexpr int kGcPackGraphs = 16;
+constexpr int kGcPackRec = 2 + kGcPackGraphs;  // ints per pack: first request, graphs, r0 of every graph
+constexpr int kGcInferStaticLds = 2048;        // bound of the kernel's static LDS (records, tile ranges)
+
+struct GcInferArgs {
+  int32_t L, kind, self_loops;
+  int32_t R;            // LDS rows of a pack: 16, 32, 48 or 64
+  int32_t D[kGcMaxLayers + 1];
+  int32_t E, C;
+  int32_t adj_of[kGcMaxLayers];
+  int32_t nadj;
+  GcAdj adj[kGcMaxAdj];
+  // the training plan's static graph tensors and parameter views (GcStepArgs)
+  int32_t G;
+  const int32_t* rec;
+  const int32_t* fpair;
+  const float* fw;
+  const float* table;
+  int32_t tab_rows;
+  const float* W[kGcMaxLayers];
+  const float* Wf[kGcMaxLayers];
+  const float* bl[kGcMaxLayers];
+  const float* eps[kGcMaxLayers];
+  const float* Wfc;
+  const float* bfc;
+  const float* Wout;
+  // the call
+  int32_t n, npacks;
+  const int32_t* gidx;  // [n] requested graphs
+  const int32_t* pack;  // [npacks][kGcPackRec]
+  float* logits;        // [n][C], request order
+  float* emb;           // [n][E] pooled graph embeddings (out_fc's input)
+  // LDS layout (bytes), computed by the host: two ping-pong activation buffers [R][ldx], one
+  // aggregate Z [R][ldz], A [nadj][R][lda], 1 / cnt [nadj][R], S [R][ldsm], the table
+  // [trp][ldt], P [16][lda], the head's P X_L [16][ldx] and pooled [16][ldpe]
+  int32_t lds_x[2], lds_z, lds_a, lds_invc, lds_s, lds_t, lds_p, lds_px, lds_pe, lds_bytes;
+  int32_t ldx, ldz, lda, ldsm, ldt, ldpe, trp;
+};
+
 }  // namespace euler_hip
 
 extern "C" {
+hipError_t eh_gc_infer(const euler_hip::GcInferArgs* a, hipStream_t s);
 hipError_t eh_gc_step(const euler_hip::GcStepArgs* a, hipStream_t s);
 hipError_t eh_gc_reduce(const euler_hip::GcReduceArgs* a, hipStream_t s);
 }

@@ -190,6 +190,40 @@ class GraphEstimator(BaseEstimator):
     def infer_input_fn(self):
         return self.get_input_from_id_file()
 
+    # device path (device_graph=True): the id file's graph labels go straight to the trainer
+    # (GraphTrainer.infer_logits / infer_embed; the fused trainers score them in one launch per
+    # batch), with none of _graph_inputs' engine queries
+    def _device_evaluate(self, tr):
+        met = getattr(self.model, "metric", None)
+        if met is not None and hasattr(met, "reset"):
+            met.reset()
+        losses, res, n, t0 = [], {}, 0, time.time()
+        for labels in self._eval_batches():
+            _, logits, y = tr.infer_logits(labels)
+            losses.append(float(F.binary_cross_entropy_with_logits(logits, y)))
+            value = met(y.cpu(), torch.sigmoid(logits).cpu()) if met is not None else float("nan")
+            res = {"loss": float(np.mean(losses)), "accuracy": float(value)}
+            n += len(labels)
+            if self.evaluate_stop_onetime:
+                break
+        if self.rank == 0:
+            log.info("evaluate: %s over %d batches (device path, %.1f graphs/s)", res, len(losses),
+                     n / max(time.time() - t0, 1e-9))
+        return res
+
+    def _device_infer(self, tr):
+        ids_out, emb_out = [], []
+        n, t0 = 0, time.time()
+        for labels in self.infer_input_fn():
+            emb = tr.infer_embed(labels)
+            ids_out.append(np.asarray(labels))
+            emb_out.append(emb.float().cpu().numpy())
+            n += len(labels)
+        self.infer_rate = n / max(time.time() - t0, 1e-9)
+        if self.rank == 0:
+            log.info("infer: %d graph embeddings (device path, %.1f graphs/s)", n, self.infer_rate)
+        return self._write_infer(ids_out, emb_out)
+
 
 class SampleEstimator(BaseEstimator):
     """Explicit CSV sample rows, repeated ``epoch`` times for training

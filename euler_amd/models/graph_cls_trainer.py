@@ -23,6 +23,11 @@ The draw is the generic trainer's (the alias table on the graph RNG's Philox str
 the advanced counter), so both trainers see the same graphs from the same RNG state;
 ``tests/test_graph_cls_trainer.py`` pins the loss and every gradient against an fp32
 torch oracle.
+
+``infer_logits`` / ``infer_embed`` (evaluate / infer of the estimator) score an explicit list
+of graphs in one launch of the forward-only kernel (``csrc/hip/graph_cls_infer.hip``), which
+packs up to 16 requested graphs into a block's 64 LDS rows and reads the same static tensors
+and parameter views (``tests/test_graph_cls_infer.py``, ``docs/DESIGN.md`` 9b-1).
 """
 from __future__ import annotations
 
@@ -269,6 +274,17 @@ class GraphClsTrainer(GraphTrainer):
         """the step without the optimizer (tests): loss_out and the flat gradient"""
         self.plan.step()
         return self.loss_out
+
+    # ------------------------------------------------------------------ inference
+    def _infer(self, gidx):
+        """one launch of the forward-only pack kernel (``csrc/hip/graph_cls_infer.hip``) over
+        the plan's static tensors and the current weights; no RNG, slab or counter is touched"""
+        dev = self.gnodes.device
+        n = int(gidx.numel())
+        logits = torch.empty(n, int(self.onehot.shape[1]), dtype=torch.float32, device=dev)
+        emb = torch.empty(n, int(self.gnn.fc.weight.shape[0]), dtype=torch.float32, device=dev)
+        self.plan.infer(gidx.to(torch.int32).contiguous(), logits, emb)
+        return emb, logits
 
     @property
     def launches_per_step(self) -> int:

@@ -113,6 +113,10 @@ class GraphTrainer(CapturedTrainer):
         return e
 
     def _forward(self, gidx):
+        return self.model.out_fc(self._pooled(gidx)).float()
+
+    def _pooled(self, gidx):
+        """the pooled graph embeddings of B graphs (``_PooledGraphModel.embed``: out_fc's input)"""
         roots = self.gnodes[gidx].reshape(-1)
         graph_of = torch.where(roots >= 0, self.slot_graph, torch.full_like(self.slot_graph, -1))
         df = self.flow.produce(roots)
@@ -121,8 +125,7 @@ class GraphTrainer(CapturedTrainer):
             x_t = mp_ops.gather(x, block.res_n_id)
             x = F.relu(self.gnn.calculate_conv(conv, (x_t, x), block.edge_index, size=block.size))
         node_emb = self.gnn.fc(x)
-        pooled = self.model.pool(node_emb, graph_of, self.B)
-        return self.model.out_fc(pooled).float()
+        return self.model.pool(node_emb, graph_of, self.B)
 
     def _materialize(self):
         if not any(isinstance(p, torch.nn.parameter.UninitializedParameter) for p in self.model.parameters()):
@@ -154,6 +157,64 @@ class GraphTrainer(CapturedTrainer):
 
     def reset_metric(self):
         self.right.zero_()
+
+    # ------------------------------------------------------------------ inference
+    def graph_index(self, graphs) -> torch.Tensor:
+        """graph indices (int64, host) of ``graphs``: a list of graph-label strings (an id
+        file's batch) or an integer index tensor / array"""
+        if isinstance(graphs, (torch.Tensor, np.ndarray)):
+            idx = torch.as_tensor(graphs).reshape(-1).long().cpu()
+        else:
+            if getattr(self, "_label_index", None) is None:
+                import euler_amd.ops.graph_api as ge
+
+                labels = list(ge.get_engine().meta().get("graph_labels", []))
+                self._label_index = {str(s): i for i, s in enumerate(labels)}
+            try:
+                idx = torch.tensor([self._label_index[str(s)] for s in graphs], dtype=torch.int64)
+            except KeyError as e:
+                raise ValueError(f"unknown graph label {e.args[0]!r}") from None
+        G = int(self.onehot.shape[0])
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= G):
+            raise ValueError(f"graph index outside [0, {G})")
+        return idx
+
+    def _infer(self, gidx):
+        """(pooled embeddings [n, E], logits [n, C]) of graph indices: the training forward
+        without gradients, in chunks padded to B graphs (the flow's capacity is B * max_nodes)"""
+        dev = self.gnodes.device
+        self._materialize()
+        embs, logits = [], []
+        state = self.graph.rng.clone()
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                for c0 in range(0, gidx.numel(), self.B):
+                    chunk = gidx[c0:c0 + self.B]
+                    k = chunk.numel()
+                    pad = torch.cat([chunk, chunk[:1].expand(self.B - k)]).to(dev)
+                    pooled = self._pooled(pad)[:k]
+                    embs.append(pooled.float())
+                    logits.append(self.model.out_fc(pooled).float())
+        finally:
+            self.model.train()
+            self.graph.rng.copy_(state)
+        if not embs:
+            E, C = self.model.out_fc.weight.shape[1], self.onehot.shape[1]
+            return torch.zeros(0, E, device=dev), torch.zeros(0, C, device=dev)
+        return torch.cat(embs), torch.cat(logits)
+
+    def infer_logits(self, graphs):
+        """(graph indices [n], logits [n, C], one-hot labels [n, C]) of ``graphs`` (label
+        strings or indices) with the current weights, everything on the trainer's device"""
+        gidx = self.graph_index(graphs)
+        _, logits = self._infer(gidx)
+        gidx = gidx.to(self.gnodes.device)
+        return gidx, logits, self.onehot[gidx]
+
+    def infer_embed(self, graphs):
+        """pooled graph embeddings [n, E] (``_PooledGraphModel.embed``) of ``graphs``"""
+        return self._infer(self.graph_index(graphs))[0]
 
     # ------------------------------------------------------------------ oracle
     def graph_labels_of(self, gidx):
