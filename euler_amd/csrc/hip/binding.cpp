@@ -545,6 +545,8 @@ PYBIND11_MODULE(_hip_ops, m) {
   register_gcn_csr_ops(gc);
   auto kb = m.def_submodule("knn_bf16");
   register_knn_bf16_ops(kb);
+  auto kgr = m.def_submodule("knn_grouped");
+  register_knn_grouped_ops(kgr);
   auto kp = m.def_submodule("kg_proj");
   register_kg_proj_ops(kp);
   auto kr = m.def_submodule("kg_transr");

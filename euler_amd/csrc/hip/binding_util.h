@@ -52,6 +52,9 @@ void register_gcn_csr_ops(py::module& m);
 // binding_knn.cpp: the searches over bf16 tables, knn_bf16.hip (registered on the submodule
 // _hip_ops.knn_bf16; partials go to knn_merge of register_knn_ops)
 void register_knn_bf16_ops(py::module& m);
+// binding_knn_grouped.cpp: the IVF search grouped by list, knn_grouped.hip (registered on the
+// submodule _hip_ops.knn_grouped; partials go to knn_merge of register_knn_ops)
+void register_knn_grouped_ops(py::module& m);
 // binding_kg_proj.cpp: TransH / TransD scores with the projection inside the score kernel,
 // kg_proj.hip (registered on the submodule _hip_ops.kg_proj)
 void register_kg_proj_ops(py::module& m);

@@ -58,17 +58,6 @@ __device__ __forceinline__ float16_t kb_mfma(uint4_t a, uint4_t b, float16_t c) 
                                                  c, 0, 0, 0);
 }
 
-// 8 bf16 starting at p, the first `valid` of them in range (the rest zero), by 2-byte loads
-__device__ __forceinline__ uint4_t kb_load8_scalar(const bf16_t* __restrict__ p, int valid) {
-  uint4_t v = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const uint32_t h = e < valid ? p[e] : 0u;
-    v[e >> 1] |= h << (16 * (e & 1));
-  }
-  return v;
-}
-
 // sum_e q[e] * x_e + acc over the 8 bf16 of v
 __device__ __forceinline__ float kb_dot8(const float (&q)[8], uint4_t v, float acc) {
 #pragma unroll

@@ -1,6 +1,7 @@
 // Device helpers and limits shared by the k-nearest-neighbour kernels (knn.hip: fp32 tables,
-// knn_bf16.hip: bf16 tables): the sorted k-best list in LDS with its threshold, and the
-// launchers' grid cap.  Ordering rule and partial format: see knn.hip.
+// knn_bf16.hip: bf16 tables, knn_grouped.hip: the list-grouped IVF search over both): the sorted
+// k-best list in LDS with its threshold, the unaligned bf16 load, and the launchers' grid cap.
+// Ordering rule and partial format: see knn.hip.
 #pragma once
 #include "hip/common.h"
 
@@ -64,6 +65,17 @@ __device__ __forceinline__ void knn_wave_select(float s, int off, bool valid, vo
       to = lo[k - 1];
     }
   }
+}
+
+// 8 bf16 starting at p, the first `valid` of them in range (the rest zero), by 2-byte loads
+__device__ __forceinline__ uint4_t kb_load8_scalar(const bf16_t* __restrict__ p, int valid) {
+  uint4_t v = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const uint32_t h = e < valid ? p[e] : 0u;
+    v[e >> 1] |= h << (16 * (e & 1));
+  }
+  return v;
 }
 
 inline int knn_grid(int64_t blocks, int64_t cap) {

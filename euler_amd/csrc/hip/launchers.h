@@ -244,6 +244,24 @@ hipError_t eh_knn_ivf_scan_bf16(const uint16_t* Q, const uint16_t* XS, const flo
 // xn [n] = sum_c x[i, c]^2 in fp32
 hipError_t eh_knn_row_norms_bf16(const uint16_t* X, int64_t n, int d, float* xn, hipStream_t s);
 
+// knn_grouped.hip (the IVF search grouped by list: a block owns one (list, tile of eh_knn_grouped_tq()
+// probing queries) and scans the list's rows with MFMA; same partial format, so eh_knn_merge follows).
+// A pair is the flat index query * nprobe + slot of a probe entry, so nq * nprobe < 2^31.
+int eh_knn_grouped_tq();
+// upper bound of the work items, from the sizes alone
+int64_t eh_knn_grouped_max_items(int64_t nq, int nprobe, int64_t ncent);
+// probe [nq, nprobe] -> qptr [ncent + 1] (pairs of list l: pairs[qptr[l] : qptr[l + 1]], in no fixed
+// order), items [max_items] (list, first pair), n_items [1].  cnt [ncent] int64 is zero on entry (scratch:
+// the histogram, then the fill cursors).  The partials of the entries that name no list (-1, out of [0, ncent)) are written here (+inf / -1).
+hipError_t eh_knn_grouped_invert(const int64_t* probe, int64_t nq, int nprobe, int64_t ncent, int k, int64_t* cnt,
+                                 int32_t* qptr, int32_t* pairs, int32_t* items, int32_t* n_items, float* pd,
+                                 int64_t* pr, hipStream_t s);
+// writes pd / pr [nq, nprobe, k] at every pair of the table; Q / XS are fp32, or raw bf16 bits (bf16 != 0)
+hipError_t eh_knn_grouped_scan(const void* Q, const void* XS, int bf16, const float* xn, const int64_t* list_ptr,
+                               const int64_t* row_of, const int32_t* qptr, const int32_t* pairs, const int32_t* items,
+                               const int32_t* n_items, int64_t max_items, int64_t nq, int64_t n, int64_t ncent,
+                               int nprobe, int d, int k, float* pd, int64_t* pr, hipStream_t s);
+
 // sage_csr.hip (full-neighbourhood GraphSAGE layer over the graph's own CSR: weight-normalised
 // mean of x over the masked (row, type) segments, then act([x_self | ns * mean + ss * x_self] @ W^T)).
 // x [N, Dp] bf16 / fp32 (Dp % 16 == 0, <= 512), W [Hp, 2 Dp] bf16 row-major (Hp % 64 == 0),

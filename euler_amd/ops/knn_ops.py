@@ -1,8 +1,8 @@
 """Fused distance + top-k search ops behind ``euler_amd.tools.knn``.
 
 * ``flat_topk(q, x, k)``  — exact k nearest rows of ``x`` for every query;
-* ``ivf_topk(q, xs, list_ptr, row_of, probe, k)`` — the same over the inverted lists a
-  query probes;
+* ``ivf_topk(q, xs, list_ptr, row_of, probe, k, schedule="query")`` — the same over the
+  inverted lists a query probes;
 * ``nearest(q, x)``       — ``flat_topk`` with ``k = 1`` (k-means / coarse assignment).
 
 Ordering rule: results are ordered by the pair (squared distance, original row), ascending,
@@ -21,6 +21,13 @@ Inverted lists are a CSR: ``xs`` is the database permuted so that list ``l`` is 
 Inside a list the positions must be in ascending original-row order (a stable sort by
 list gives that); ties inside a list are then decided by position.
 
+``ivf_topk`` has two schedules with one result.  ``"query"`` (the default) gives one wave to
+each (query, probed list) pair: right for a handful of queries.  ``"list"`` groups the work by
+list (``csrc/hip/knn_grouped.hip``): the probe table is inverted on the device, and a block
+scans a list once for a tile of ``LIST_TQ`` of the queries that probe it, on the matrix units:
+right for a large batch, where many queries meet in a list.  Nothing is read back to the host
+on the way.  Both serve fp32 and bf16 tables; the twin does not depend on the schedule.
+
 The table's dtype picks the path.  A bfloat16 ``x`` / ``xs`` is searched in place, with bf16
 matrix instructions and fp32 sums (exact products, so the result is that of fp32 arithmetic
 on the bf16 values); no fp32 copy of the table is made, on the GPU or in the twin.  Its
@@ -33,9 +40,13 @@ import torch
 
 from euler_amd.ops._native import hip, use_hip
 
-__all__ = ["flat_topk", "ivf_topk", "nearest", "build_lists", "row_norms", "MAX_KERNEL_K"]
+__all__ = ["flat_topk", "ivf_topk", "nearest", "build_lists", "row_norms", "MAX_KERNEL_K", "LIST_TQ", "SCHEDULES"]
 
 MAX_KERNEL_K = 128
+# queries per work item of the "list" schedule: kGrTQ of knn_grouped.hip, repeated here because a CPU
+# import cannot ask the binding; tests/test_knn_grouped.py holds the two equal (knn_grouped.tq)
+LIST_TQ = 64
+SCHEDULES = ("query", "list")
 _MAX_SPLITS = 64
 _TARGET_BLOCKS = 512  # two resident blocks on each of the 256 CUs
 
@@ -186,13 +197,22 @@ def nearest(q, x, xn=None):
     return flat_topk(q, x, 1, xn=xn)[1][:, 0]
 
 
-def ivf_topk(q, xs, list_ptr, row_of, probe, k, xn=None):
+def check_schedule(schedule):
+    if schedule not in SCHEDULES:
+        raise ValueError("schedule must be one of %s, got %r" % (" | ".join(SCHEDULES), schedule))
+    return schedule
+
+
+def ivf_topk(q, xs, list_ptr, row_of, probe, k, xn=None, schedule="query"):
     """``(D, I)`` over the lists in ``probe [nq, nprobe]`` (``-1``: none); ``I`` holds
     original rows.  See the module docstring for the CSR layout; a bfloat16 ``xs`` is searched in
-    place with bf16 queries (an fp32 ``q`` is rounded to bf16 once)."""
+    place with bf16 queries (an fp32 ``q`` is rounded to bf16 once).  ``schedule``: ``"query"``
+    (one wave per (query, list)) or ``"list"`` (the queries of a list scan it together); the
+    result is the same."""
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")
+    check_schedule(schedule)
     bf = xs.dtype == torch.bfloat16
     if bf:
         q, xs = _bf16(q), xs.contiguous()
@@ -209,6 +229,11 @@ def ivf_topk(q, xs, list_ptr, row_of, probe, k, xn=None):
         return _empty_result(q.shape[0], k, q.device)
     if not use_hip(q, xs, xn, list_ptr, row_of, probe) or k > MAX_KERNEL_K or probe.shape[1] > _MAX_SPLITS:
         return _ivf_topk_torch(q.float(), xs, list_ptr, row_of, probe, k, xn)
+    if schedule == "list":
+        grouped = hip().knn_grouped
+        qptr, pairs, items, n_items, pd, pr = grouped.invert(probe, list_ptr.numel() - 1, k)
+        grouped.scan(q, xs, xn, list_ptr, row_of, qptr, pairs, items, n_items, pd, pr)
+        return tuple(hip().knn_merge(pd, pr, _norms(q.float())))
     scan = hip().knn_bf16.ivf_scan if bf else hip().knn_ivf_scan
     pd, pr = scan(q, xs, xn, list_ptr, row_of, probe, k)
     return tuple(hip().knn_merge(pd, pr, _norms(q.float())))

@@ -14,6 +14,13 @@ no distance matrix is allocated, equal distances go to the lower row, the invert
 are a CSR).  CPU tensors, and ``use_kernels=False`` on any device, take the torch
 composition: GEMMs through ``torch.matmul``, ``torch.topk`` selections, padded lists.
 
+``IVFFlatIndex(..., schedule="list")`` (CLI ``--ivf_schedule list``) groups the IVF search by
+list instead of by query: the queries that probe a list scan it together on the matrix units,
+and the search takes its queries 65,536 at a time instead of 1,024.  It is meant for large query
+batches (neighbours of every node); the results are those of the default ``"query"`` schedule.
+Where the kernels do not apply (CPU tensors, ``use_kernels=False``, ``k`` or ``nprobe`` past their
+limits) a ``"list"`` index runs the ops' twin, and with ``use_kernels=False`` no kernel at all.
+
 ``dtype=torch.bfloat16`` keeps the table (and the IVF index's list-ordered copy) in bf16 and
 searches it in place with the bf16 kernels: half the memory, no fp32 copy at any point, a GPU
 bf16 tensor of ``infer()`` is adopted as it is.  Queries are rounded to bf16; distances are
@@ -23,7 +30,8 @@ index has no torch composition: off the GPU (or past ``k = 128``) it runs the op
 CLI (same flags as the reference)::
 
     python -m euler_amd.tools.knn --embedding_file embedding_0.npy --id_file ids_0.npy \
-        [--query_file q.csv] [--index_type ivfflat|flat] [--k 10] [--out result.npz] [--dtype fp32|bf16]
+        [--query_file q.csv] [--index_type ivfflat|flat] [--k 10] [--out result.npz] [--dtype fp32|bf16] \
+        [--ivf_schedule query|list]
 
 ``--embedding_file`` / ``--id_file`` also take comma-separated lists of equal length (the
 per-rank files of a multi-rank ``infer()``), concatenated in order.
@@ -156,8 +164,9 @@ def kmeans(x, ncent, iters=20, seed=0, min_points_per_centroid=4, use_kernels=No
 
 class IVFFlatIndex:
     def __init__(self, d, ncent, nprobe=10, device=None, min_points_per_centroid=4, iters=20, use_kernels=None,
-                 dtype=torch.float32):
+                 dtype=torch.float32, schedule="query"):
         self.d, self.ncent, self.nprobe = d, int(ncent), int(nprobe)
+        self.schedule = knn_ops.check_schedule(schedule)
         self.device = _dev(device)
         self.dtype = _table_dtype(dtype, use_kernels)
         self.use_kernels = _kernels(use_kernels, self.device)
@@ -188,7 +197,7 @@ class IVFFlatIndex:
             self.xb = x if self.xb is None else torch.cat([self.xb, x])
             self.assign = _assign(self.xb, self.cent, self.use_kernels)
             self.xn = (self.xb * self.xb).sum(1)
-        if self.use_kernels or self.dtype == torch.bfloat16:
+        if self.use_kernels or self.dtype == torch.bfloat16 or self.schedule == "list":
             # CSR inverted lists: the database in list order, original order kept inside a list
             self.list_ptr, self.row_of = knn_ops.build_lists(self.assign, self.ncent)
             self.xs, self.xns = self.xb[self.row_of], self.xn[self.row_of]
@@ -213,20 +222,33 @@ class IVFFlatIndex:
     def ntotal(self):
         return 0 if self.xb is None else self.xb.shape[0]
 
-    def search(self, q, k, chunk=1024):
+    def search(self, q, k, chunk=None):
+        """``chunk``: queries per pass; None is 1024, or 65,536 under ``schedule="list"``, where
+        grouping only pays when many queries meet in a list"""
+        if chunk is None:
+            chunk = 65536 if self.schedule == "list" else 1024
         q = _queries(q, self.dtype, self.device)
         nprobe = min(self.nprobe, self.ncent)
         ds, ids = [], []
         fused = self.use_kernels and 1 <= int(k) <= knn_ops.MAX_KERNEL_K and nprobe <= 64
-        fused = fused or self.dtype == torch.bfloat16  # the ops' twin serves what the kernels do not
+        # the ops' twin serves what the kernels do not
+        fused = fused or self.dtype == torch.bfloat16 or self.schedule == "list"
+        # an fp32 "list" index without the kernels (use_kernels=False, or off the GPU): no kernel on any
+        # device, the probe selection by torch and the IVF step by the ops' twin
+        twin = self.schedule == "list" and not self.use_kernels and self.dtype == torch.float32
         if not fused and self.lists is None:
             self._pad_lists()
         for s in range(0, q.shape[0], chunk):
             qq = q[s:s + chunk]
             if fused:
-                probe = knn_ops.flat_topk(qq, self.cent, nprobe)[1]
                 kk = min(int(k), nprobe * max(self.maxl, 1))  # as many columns as the padded table gives
-                v, got = knn_ops.ivf_topk(qq, self.xs, self.list_ptr, self.row_of, probe, kk, xn=self.xns)
+                if twin:
+                    probe = torch.topk(_sqdist(qq, self.cent), nprobe, dim=1, largest=False).indices
+                    v, got = knn_ops._ivf_topk_torch(qq, self.xs, self.list_ptr, self.row_of, probe, kk, self.xns)
+                else:
+                    probe = knn_ops.flat_topk(qq, self.cent, nprobe)[1]
+                    v, got = knn_ops.ivf_topk(qq, self.xs, self.list_ptr, self.row_of, probe, kk, xn=self.xns,
+                                              schedule=self.schedule)
                 ds.append(v)
                 ids.append(got)
                 continue
@@ -247,16 +269,19 @@ class IVFFlatIndex:
 
 
 def build_index(embedding, index_type="ivfflat", device=None, use_kernels=None, max_points_per_centroid=None,
-                dtype=torch.float32):
-    """``max_points_per_centroid`` caps the k-means training set at that many points per
+                dtype=torch.float32, schedule="query"):
+    """``schedule`` is the IVF index's search schedule, ``"query"`` or ``"list"`` (a flat index has none).
+    ``max_points_per_centroid`` caps the k-means training set at that many points per
     centroid (a seeded random subset; faiss uses 256); None trains on everything (in fp32, for
     a bf16 index too).  ``dtype``: the table's storage, ``torch.float32`` or ``torch.bfloat16``."""
     n, d = embedding.shape
+    knn_ops.check_schedule(schedule)
     if index_type == "flat":
         idx = FlatIndex(d, device, use_kernels=use_kernels, dtype=dtype)
     elif index_type == "ivfflat":
         ncent = int(4 * math.sqrt(n))
-        idx = IVFFlatIndex(d, ncent, nprobe=10, device=device, use_kernels=use_kernels, dtype=dtype)
+        idx = IVFFlatIndex(d, ncent, nprobe=10, device=device, use_kernels=use_kernels, dtype=dtype,
+                           schedule=schedule)
         train = embedding
         if max_points_per_centroid is not None and n > int(max_points_per_centroid) * max(ncent, 1):
             g = torch.Generator(device="cpu").manual_seed(1234)
@@ -280,6 +305,8 @@ def main(argv=None):
     p.add_argument("--device", default=None)
     p.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
                    help="storage of the table: bf16 halves the memory and searches with the bf16 kernels")
+    p.add_argument("--ivf_schedule", choices=list(knn_ops.SCHEDULES), default="query",
+                   help="IVF search grouped by query (default) or by list (large query batches)")
     p.add_argument("--max_points_per_centroid", type=int, default=None,
                    help="cap on the k-means training set per centroid (faiss uses 256; default: no cap)")
     a = p.parse_args(argv)
@@ -293,7 +320,7 @@ def main(argv=None):
         ids = np.arange(len(emb))
     assert len(ids) == len(emb), "ids and embeddings differ in length"
     index = build_index(emb, a.index_type, a.device, max_points_per_centroid=a.max_points_per_centroid,
-                        dtype=torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+                        dtype=torch.bfloat16 if a.dtype == "bf16" else torch.float32, schedule=a.ivf_schedule)
     query = np.loadtxt(a.query_file, dtype=np.float32, delimiter=",", ndmin=2) if a.query_file else emb[:25]
     D, I = index.search(query, a.k)
     res_ids = np.where(I >= 0, ids[np.clip(I, 0, None)], -1)
