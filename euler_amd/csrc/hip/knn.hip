@@ -52,19 +52,13 @@ __global__ __launch_bounds__(kKnnThreads) void knn_flat_scan_kernel(const float*
                                                                     int64_t* __restrict__ pr) {
   constexpr int NWQ = TQ / 32;        // waves along the queries
   constexpr int NB = 2 / (4 / NWQ);   // 32-row column blocks per wave
-  constexpr int QW = TQ / 4;          // queries owned per wave in the selection
   constexpr int NLOAD = (TQ + kKnnTR) * kKnnKC / kKnnThreads;  // staged floats per thread and chunk
   extern __shared__ __align__(16) float knn_smem[];
   float* As = knn_smem;                          // [TQ][kKnnLd]
   float* Bs = As + TQ * kKnnLd;                  // [64][kKnnLd]
   float* xns = Bs + kKnnTR * kKnnLd;             // [64]
   float* sc = xns + kKnnTR;                      // [TQ][kKnnScLd]
-  float* st_td = sc + TQ * kKnnScLd;             // [TQ] threshold score
-  int* st_to = reinterpret_cast<int*>(st_td + TQ);   // [TQ] threshold offset
-  int* st_c = st_to + TQ;                        // [TQ] entries held
-  int* qflag = st_c + TQ;                        // [TQ] tile has a candidate
-  float* ld = reinterpret_cast<float*>(qflag + TQ);  // [TQ][k]
-  int* lo = reinterpret_cast<int*>(ld + static_cast<size_t>(TQ) * k);  // [TQ][k]
+  const KnnSel<TQ, 1> st(sc + TQ * kKnnScLd, k);  // one flag per query: the tile has a candidate
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
@@ -82,14 +76,10 @@ __global__ __launch_bounds__(kKnnThreads) void knn_flat_scan_kernel(const float*
     int64_t t_end = t_begin + tiles_per_split;
     if (t_end > ntiles) t_end = ntiles;
     const int64_t r_begin = t_begin * kKnnTR;
+    const int live = knn_count(nq - q0, TQ);  // queries of the tile that exist
 
     __syncthreads();  // the previous item's lists and state are written out
-    for (int i = tid; i < TQ; i += kKnnThreads) {
-      st_td[i] = inf;
-      st_to[i] = INT_MAX;
-      st_c[i] = 0;
-      qflag[i] = 0;
-    }
+    st.reset();
 
     float stage[NLOAD];
     float stage_xn = 0.f;
@@ -185,60 +175,25 @@ __global__ __launch_bounds__(kKnnThreads) void knn_flat_scan_kernel(const float*
         const float xv = xns[j];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = wq * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int i = wq * 32 + knn_c_row(r, h);
           const float s = rv ? fmaf(-2.f, acc[b][r], xv) : inf;
           sc[i * kKnnScLd + j] = s;
-          if (rv && s <= st_td[i]) qflag[i] = 1;
+          if (rv && s <= st.td[i]) st.flag[i] = 1;
         }
       }
       __syncthreads();
-
-      // selection: wave w owns queries [w * QW, (w + 1) * QW)
-      const int myq = w * QW + lane;
-      const bool flagged = lane < QW && qflag[myq] != 0;
-      if (flagged) qflag[myq] = 0;
-      uint64_t qm = __ballot(flagged);
-      const int toff = static_cast<int>(x0 - r_begin);
-      while (qm) {
-        const int qq = __ffsll(static_cast<unsigned long long>(qm)) - 1;
-        qm &= qm - 1;
-        const int ql = w * QW + qq;
-        if (q0 + ql >= nq) break;
-        int c = st_c[ql];
-        float td = st_td[ql];
-        int to = st_to[ql];
-        const float s = sc[ql * kKnnScLd + lane];
-        knn_wave_select(s, toff + lane, x0 + lane < n, ld + static_cast<size_t>(ql) * k,
-                        lo + static_cast<size_t>(ql) * k, k, c, td, to);
-        if (lane == 0) {
-          st_c[ql] = c;
-          st_td[ql] = td;
-          st_to[ql] = to;
-        }
-      }
+      st.select(0, sc, kKnnScLd, 0, live, static_cast<int>(x0 - r_begin), 0, knn_count(n - x0, kKnnTR));
     }
 
-    // write the partial lists of this (query tile, split): each wave its own queries
+    // write the partial lists of this (query tile, split)
     __syncthreads();
-    for (int qq = 0; qq < QW; ++qq) {
-      const int ql = w * QW + qq;
-      const int64_t qg = q0 + ql;
-      if (qg >= nq) break;
-      const int c = st_c[ql];
-      const int64_t base = (qg * S + split) * k;
-      for (int j = lane; j < k; j += 64) {
-        const bool has = j < c;
-        pd[base + j] = has ? ld[static_cast<size_t>(ql) * k + j] : inf;
-        pr[base + j] = has ? r_begin + lo[static_cast<size_t>(ql) * k + j] : int64_t{-1};
-      }
-    }
+    st.write_back(0, live, pd, pr, [&](int ql) { return ((q0 + ql) * S + split) * k; }, KnnRowBase{r_begin});
   }
 }
 
-template <int TQ>
-size_t knn_flat_lds(int k) {
-  return sizeof(float) * (static_cast<size_t>(TQ) * kKnnLd + kKnnTR * kKnnLd + kKnnTR + TQ * kKnnScLd + 4 * TQ +
-                          2 * static_cast<size_t>(TQ) * k);
+size_t knn_flat_lds(int tq, int k) {
+  return sizeof(float) * (static_cast<size_t>(tq) * kKnnLd + kKnnTR * kKnnLd + kKnnTR + tq * kKnnScLd) +
+         knn_sel_bytes(tq, 1, 0, k);
 }
 
 // ---------------------------------------------------------------------------------- IVF
@@ -263,13 +218,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_ivf_scan_kernel(const float* 
     const int64_t qi = item / nprobe;
     const int64_t list = probe[item];
     int64_t b = 0, e = 0;
-    if (list >= 0 && list < ncent) {
-      b = list_ptr[list];
-      e = list_ptr[list + 1];
-      if (b < 0) b = 0;
-      if (e > n) e = n;
-      if (e - b > INT_MAX - 64) e = b + (INT_MAX - 64);  // offsets inside a list are 32-bit
-    }
+    if (list >= 0 && list < ncent) knn_list_range(list_ptr, list, n, 64, b, e);
     const float* q = Q + qi * d;
     float4_t qv0 = {0.f, 0.f, 0.f, 0.f};
     float qs0 = 0.f;
@@ -316,12 +265,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_ivf_scan_kernel(const float* 
       const float s = valid ? fmaf(-2.f, mine, xn[base + lane]) : inf;
       knn_wave_select(s, static_cast<int>(base - b) + lane, valid, ld, lo, k, c, td, to);
     }
-    const int64_t ob = item * k;
-    for (int j = lane; j < k; j += 64) {
-      const bool has = j < c;
-      pd[ob + j] = has ? ld[j] : inf;
-      pr[ob + j] = has ? row_of[b + lo[j]] : int64_t{-1};
-    }
+    knn_write_partial(ld, lo, c, k, pd, pr, item * k, KnnRowOf{row_of, b});
   }
 }
 
@@ -390,47 +334,19 @@ extern "C" {
 
 hipError_t eh_knn_flat_scan(const float* Q, const float* X, const float* xn, int64_t nq, int64_t n, int d, int k,
                             int S, float* pd, int64_t* pr, hipStream_t s) {
-  if (nq <= 0 || n <= 0 || d < 1 || k < 1 || k > kKnnMaxK || S < 1 || S > kKnnMaxSplits) return hipErrorInvalidValue;
-  const int64_t ntiles = ceil_div(n, kKnnTR);
-  const int64_t tps = ceil_div(ntiles, S);
-  if (tps * kKnnTR > INT_MAX - kKnnTR) return hipErrorInvalidValue;  // offsets inside a split are 32-bit
-  const bool vec = d % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0;
-  const bool wide = k <= 32;  // 128-query tiles while the lists fit beside two resident blocks
-  const int64_t nqt = ceil_div(nq, wide ? 128 : 64);
-  const int64_t items = nqt * S;
-  const int grid = knn_grid(items, 4096);
-#define EH_KNN_FLAT(TQ, V)                                                                                     \
-  do {                                                                                                         \
-    const size_t lds = knn_flat_lds<TQ>(k);                                                                    \
-    if (lds > 65536)                                                                                           \
-      EULER_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_flat_scan_kernel<TQ, V>),          \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds))); \
-    hipLaunchKernelGGL((knn_flat_scan_kernel<TQ, V>), dim3(grid), dim3(kKnnThreads), lds, s, Q, X, xn, nq, n, d, k, \
-                       S, tps, items, pd, pr);                                                                 \
-  } while (0)
-  if (wide) {
-    if (vec) EH_KNN_FLAT(128, true); else EH_KNN_FLAT(128, false);
-  } else {
-    if (vec) EH_KNN_FLAT(64, true); else EH_KNN_FLAT(64, false);
-  }
-#undef EH_KNN_FLAT
-  return hipGetLastError();
+  static const knn_flat_kernel_t<float> kern[2][2] = {
+      {knn_flat_scan_kernel<64, false>, knn_flat_scan_kernel<64, true>},
+      {knn_flat_scan_kernel<128, false>, knn_flat_scan_kernel<128, true>}};
+  return knn_flat_launch(kern, kKnnTR, 4, knn_flat_lds, Q, X, xn, nq, n, d, k, S, pd, pr, s);
 }
 
 hipError_t eh_knn_ivf_scan(const float* Q, const float* XS, const float* xn, const int64_t* list_ptr,
                            const int64_t* row_of, const int64_t* probe, int64_t nq, int64_t n, int64_t ncent,
                            int nprobe, int d, int k, float* pd, int64_t* pr, hipStream_t s) {
-  if (nq <= 0 || n < 0 || ncent < 1 || nprobe < 1 || nprobe > kKnnMaxSplits || d < 1 || k < 1 || k > kKnnMaxK)
-    return hipErrorInvalidValue;
-  const bool vec = d % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(XS) % 16 == 0;
-  const int grid = knn_grid(ceil_div(nq * nprobe, kKnnThreads / 64), 1 << 16);
-  const size_t lds = sizeof(float) * 2 * k * (kKnnThreads / 64);
-  if (vec)
-    hipLaunchKernelGGL(knn_ivf_scan_kernel<true>, dim3(grid), dim3(kKnnThreads), lds, s, Q, XS, xn, list_ptr, row_of,
-                       probe, nq, n, ncent, nprobe, d, k, pd, pr);
-  else
-    hipLaunchKernelGGL(knn_ivf_scan_kernel<false>, dim3(grid), dim3(kKnnThreads), lds, s, Q, XS, xn, list_ptr, row_of,
-                       probe, nq, n, ncent, nprobe, d, k, pd, pr);
+  KnnIvfPlan p;
+  EULER_HIP_CHECK(knn_ivf_plan(Q, XS, 4, nq, n, ncent, nprobe, d, k, p));
+  hipLaunchKernelGGL(p.vec ? knn_ivf_scan_kernel<true> : knn_ivf_scan_kernel<false>, dim3(p.grid), dim3(kKnnThreads),
+                     p.lds, s, Q, XS, xn, list_ptr, row_of, probe, nq, n, ncent, nprobe, d, k, pd, pr);
   return hipGetLastError();
 }
 

@@ -45,18 +45,11 @@ namespace euler_hip {
 
 namespace {
 
-typedef __bf16 kb_bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kBfTR = 128;          // rows of X per tile
 constexpr int kBfHR = 64;           // rows per score half tile
 constexpr int kBfKC = 64;           // columns of d per LDS chunk
 constexpr int kBfLd = kBfKC + 8;    // staging row stride (halfwords)
 constexpr int kBfScLd = kBfHR + 1;  // score row stride (floats)
-
-__device__ __forceinline__ float16_t kb_mfma(uint4_t a, uint4_t b, float16_t c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(kb_bf16x8, a), __builtin_bit_cast(kb_bf16x8, b),
-                                                 c, 0, 0, 0);
-}
 
 // sum_e q[e] * x_e + acc over the 8 bf16 of v
 __device__ __forceinline__ float kb_dot8(const float (&q)[8], uint4_t v, float acc) {
@@ -86,19 +79,13 @@ __global__ __launch_bounds__(kKnnThreads, TQ == 128 ? 2 : 3) void knn_flat_scan_
   constexpr int NWQ = TQ / 64;  // waves along the queries, 64 queries each
   constexpr int NWR = 4 / NWQ;  // waves along the rows
   constexpr int NB = 4 / NWR;   // 32-row blocks of the tile per wave: block b * NWR + wr
-  constexpr int QW = TQ / 4;    // queries owned per wave in the selection
   constexpr int NU = (TQ + kBfTR) * (kBfKC / 8) / kKnnThreads;  // staged 16-byte units per thread and chunk
   extern __shared__ __align__(16) unsigned char knnb_smem[];
   bf16_t* Qs = reinterpret_cast<bf16_t*>(knnb_smem);  // [TQ][kBfLd]
   bf16_t* Xs = Qs + TQ * kBfLd;                        // [128][kBfLd]
   float* sc = reinterpret_cast<float*>(knnb_smem);    // [TQ][kBfScLd], over the staging buffer
   float* xns = reinterpret_cast<float*>(Xs + kBfTR * kBfLd);  // [128], +inf past n
-  float* st_td = xns + kBfTR;                          // [TQ] threshold score
-  int* st_to = reinterpret_cast<int*>(st_td + TQ);     // [TQ] threshold offset
-  int* st_c = st_to + TQ;                              // [TQ] entries held
-  int* qflag = st_c + TQ;                              // [2][TQ] half tile has a candidate
-  float* ld = reinterpret_cast<float*>(qflag + 2 * TQ);                // [TQ][k]
-  int* lo = reinterpret_cast<int*>(ld + static_cast<size_t>(TQ) * k);  // [TQ][k]
+  const KnnSel<TQ, 2> st(xns + kBfTR, k);              // a flag per query and score half tile
   static_assert(TQ * kBfScLd * 4 <= (TQ + kBfTR) * kBfLd * 2, "the score half tile must fit the staging buffer");
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -119,13 +106,7 @@ __global__ __launch_bounds__(kKnnThreads, TQ == 128 ? 2 : 3) void knn_flat_scan_
     const int64_t r_begin = t_begin * kBfTR;
 
     __syncthreads();  // the previous item's lists and state are written out
-    for (int i = tid; i < TQ; i += kKnnThreads) {
-      st_td[i] = inf;
-      st_to[i] = INT_MAX;
-      st_c[i] = 0;
-      qflag[i] = 0;
-      qflag[TQ + i] = 0;
-    }
+    st.reset();
 
     uint4_t stage[NU];
     float stage_xn = 0.f;
@@ -195,99 +176,41 @@ __global__ __launch_bounds__(kKnnThreads, TQ == 128 ? 2 : 3) void knn_flat_scan_
 #pragma unroll
           for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < NB; ++b) acc[a][b] = kb_mfma(xf[b], qf[a], acc[a][b]);
+            for (int b = 0; b < NB; ++b) acc[a][b] = knn_mfma_bf16(xf[b], qf[a], acc[a][b]);
         }
       }
 
       // selection, 64 rows at a time: row block rb = b * NWR + wr belongs to half rb >> 1
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
-        int* flag = qflag + hf * TQ;
-        // a lane's scores of one accumulator are 16 rows against one query: flag the query if
-        // the least of them is at or under its threshold
+        // a lane's scores of one accumulator are 16 rows against one query (KnnSel::tile_flag)
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-          const bool mine = NWR == 2 ? b == hf : (wr >> 1) == hf;
-          if (!mine) continue;
           const int rb = b * NWR + wr;
-          float xv[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) xv[r] = xns[rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
-#pragma unroll
-          for (int a = 0; a < 2; ++a) {
-            const int ql = wq * 64 + a * 32 + l31;
-            float m = inf;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) m = fminf(m, fmaf(-2.f, acc[a][b][r], xv[r]));
-            if (m <= st_td[ql]) flag[ql] = 1;
-          }
+          const bool mine = NWR == 2 ? b == hf : (wr >> 1) == hf;
+          if (mine) st.tile_flag(hf, acc[0][b], acc[1][b], xns + rb * 32, wq * 64 + l31);
         }
         __syncthreads();  // flags are set; at hf = 0 the tile's last fragment reads are done too
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-          const bool mine = NWR == 2 ? b == hf : (wr >> 1) == hf;
-          if (!mine) continue;
           const int rb = b * NWR + wr;
-#pragma unroll
-          for (int a = 0; a < 2; ++a) {
-            const int ql = wq * 64 + a * 32 + l31;
-            if (flag[ql] == 0) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-              sc[ql * kBfScLd + (rb & 1) * 32 + i] = fmaf(-2.f, acc[a][b][r], xns[rb * 32 + i]);
-            }
-          }
+          const bool mine = NWR == 2 ? b == hf : (wr >> 1) == hf;
+          if (mine) st.tile_spill(hf, acc[0][b], acc[1][b], xns + rb * 32, wq * 64 + l31, sc + (rb & 1) * 32, kBfScLd);
         }
         __syncthreads();
-
-        // wave w owns queries [w * QW, (w + 1) * QW)
-        const int myq = w * QW + lane;
-        const bool flagged = lane < QW && flag[myq] != 0;
-        if (flagged) flag[myq] = 0;
-        uint64_t qm = __ballot(flagged);
         const int64_t h0 = x0 + hf * kBfHR;
-        const int toff = static_cast<int>(h0 - r_begin);
-        while (qm) {
-          const int qq = __ffsll(static_cast<unsigned long long>(qm)) - 1;
-          qm &= qm - 1;
-          const int ql = w * QW + qq;
-          if (q0 + ql >= nq) break;
-          int c = st_c[ql];
-          float td = st_td[ql];
-          int to = st_to[ql];
-          const float s = sc[ql * kBfScLd + lane];
-          knn_wave_select(s, toff + lane, h0 + lane < n, ld + static_cast<size_t>(ql) * k,
-                          lo + static_cast<size_t>(ql) * k, k, c, td, to);
-          if (lane == 0) {
-            st_c[ql] = c;
-            st_td[ql] = td;
-            st_to[ql] = to;
-          }
-        }
+        st.select(hf, sc, kBfScLd, q0, nq, static_cast<int>(h0 - r_begin), h0, n);
       }
     }
 
-    // write the partial lists of this (query tile, split): each wave its own queries
+    // write the partial lists of this (query tile, split)
     __syncthreads();
-    for (int qq = 0; qq < QW; ++qq) {
-      const int ql = w * QW + qq;
-      const int64_t qg = q0 + ql;
-      if (qg >= nq) break;
-      const int c = st_c[ql];
-      const int64_t base = (qg * S + split) * k;
-      for (int j = lane; j < k; j += 64) {
-        const bool has = j < c;
-        pd[base + j] = has ? ld[static_cast<size_t>(ql) * k + j] : inf;
-        pr[base + j] = has ? r_begin + lo[static_cast<size_t>(ql) * k + j] : int64_t{-1};
-      }
-    }
+    st.write_back(q0, nq, pd, pr, [&](int ql) { return ((q0 + ql) * S + split) * k; }, KnnRowBase{r_begin});
   }
 }
 
-template <int TQ>
-size_t knn_flat_bf16_lds(int k) {
-  return static_cast<size_t>(TQ + kBfTR) * kBfLd * 2 + sizeof(float) * (kBfTR + 5 * TQ + 2 * static_cast<size_t>(TQ) * k);
+size_t knn_flat_bf16_lds(int tq, int k) {
+  return static_cast<size_t>(tq + kBfTR) * kBfLd * 2 + sizeof(float) * kBfTR + knn_sel_bytes(tq, 2, 0, k);
 }
 
 // ---------------------------------------------------------------------------------- IVF
@@ -313,13 +236,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_ivf_scan_bf16_kernel(
     const int64_t qi = item / nprobe;
     const int64_t list = probe[item];
     int64_t b = 0, e = 0;
-    if (list >= 0 && list < ncent) {
-      b = list_ptr[list];
-      e = list_ptr[list + 1];
-      if (b < 0) b = 0;
-      if (e > n) e = n;
-      if (e - b > INT_MAX - 64) e = b + (INT_MAX - 64);  // offsets inside a list are 32-bit
-    }
+    if (list >= 0 && list < ncent) knn_list_range(list_ptr, list, n, 64, b, e);
     const bf16_t* q = Q + qi * d;
     float qv0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (W * li < d) {
@@ -374,12 +291,7 @@ __global__ __launch_bounds__(kKnnThreads) void knn_ivf_scan_bf16_kernel(
       const float s = valid ? fmaf(-2.f, mine, xn[base + lane]) : inf;
       knn_wave_select(s, static_cast<int>(base - b) + lane, valid, ld, lo, k, c, td, to);
     }
-    const int64_t ob = item * k;
-    for (int j = lane; j < k; j += 64) {
-      const bool has = j < c;
-      pd[ob + j] = has ? ld[j] : inf;
-      pr[ob + j] = has ? row_of[b + lo[j]] : int64_t{-1};
-    }
+    knn_write_partial(ld, lo, c, k, pd, pr, item * k, KnnRowOf{row_of, b});
   }
 }
 
@@ -414,8 +326,6 @@ __global__ __launch_bounds__(kKnnThreads) void knn_row_norms_bf16_kernel(const b
   }
 }
 
-bool knn_aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 // log2 of the lanes that share a row: the power of two at or above ceil(d / width), at most 64
 int knn_lane_group_log2(int d, int width) {
   const int units = (d + width - 1) / width;
@@ -434,48 +344,21 @@ extern "C" {
 
 hipError_t eh_knn_flat_scan_bf16(const uint16_t* Q, const uint16_t* X, const float* xn, int64_t nq, int64_t n, int d,
                                  int k, int S, float* pd, int64_t* pr, hipStream_t s) {
-  if (nq <= 0 || n <= 0 || d < 1 || k < 1 || k > kKnnMaxK || S < 1 || S > kKnnMaxSplits) return hipErrorInvalidValue;
-  const int64_t ntiles = ceil_div(n, kBfTR);
-  const int64_t tps = ceil_div(ntiles, S);
-  if (tps * kBfTR > INT_MAX - kBfTR) return hipErrorInvalidValue;  // offsets inside a split are 32-bit
-  const bool vec = d % 8 == 0 && knn_aligned16(Q) && knn_aligned16(X);
-  const bool wide = k <= 32;  // 128-query tiles while the lists leave room for two resident blocks
-  const int64_t nqt = ceil_div(nq, wide ? 128 : 64);
-  const int64_t items = nqt * S;
-  const int grid = knn_grid(items, 4096);
-#define EH_KNN_FLAT_BF16(TQ, V)                                                                                  \
-  do {                                                                                                           \
-    const size_t lds = knn_flat_bf16_lds<TQ>(k);                                                                 \
-    if (lds > 65536)                                                                                             \
-      EULER_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_flat_scan_bf16_kernel<TQ, V>),       \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));   \
-    hipLaunchKernelGGL((knn_flat_scan_bf16_kernel<TQ, V>), dim3(grid), dim3(kKnnThreads), lds, s, Q, X, xn, nq, n, \
-                       d, k, S, tps, items, pd, pr);                                                             \
-  } while (0)
-  if (wide) {
-    if (vec) EH_KNN_FLAT_BF16(128, true); else EH_KNN_FLAT_BF16(128, false);
-  } else {
-    if (vec) EH_KNN_FLAT_BF16(64, true); else EH_KNN_FLAT_BF16(64, false);
-  }
-#undef EH_KNN_FLAT_BF16
-  return hipGetLastError();
+  static const knn_flat_kernel_t<bf16_t> kern[2][2] = {
+      {knn_flat_scan_bf16_kernel<64, false>, knn_flat_scan_bf16_kernel<64, true>},
+      {knn_flat_scan_bf16_kernel<128, false>, knn_flat_scan_bf16_kernel<128, true>}};
+  return knn_flat_launch(kern, kBfTR, 8, knn_flat_bf16_lds, Q, X, xn, nq, n, d, k, S, pd, pr, s);
 }
 
 hipError_t eh_knn_ivf_scan_bf16(const uint16_t* Q, const uint16_t* XS, const float* xn, const int64_t* list_ptr,
                                 const int64_t* row_of, const int64_t* probe, int64_t nq, int64_t n, int64_t ncent,
                                 int nprobe, int d, int k, float* pd, int64_t* pr, hipStream_t s) {
-  if (nq <= 0 || n < 0 || ncent < 1 || nprobe < 1 || nprobe > kKnnMaxSplits || d < 1 || k < 1 || k > kKnnMaxK)
-    return hipErrorInvalidValue;
-  const bool vec = d % 8 == 0 && knn_aligned16(Q) && knn_aligned16(XS);
-  const int lg = knn_lane_group_log2(d, vec ? 8 : 1);
-  const int grid = knn_grid(ceil_div(nq * nprobe, kKnnThreads / 64), 1 << 16);
-  const size_t lds = sizeof(float) * 2 * k * (kKnnThreads / 64);
-  if (vec)
-    hipLaunchKernelGGL(knn_ivf_scan_bf16_kernel<true>, dim3(grid), dim3(kKnnThreads), lds, s, Q, XS, xn, list_ptr,
-                       row_of, probe, nq, n, ncent, nprobe, d, k, lg, pd, pr);
-  else
-    hipLaunchKernelGGL(knn_ivf_scan_bf16_kernel<false>, dim3(grid), dim3(kKnnThreads), lds, s, Q, XS, xn, list_ptr,
-                       row_of, probe, nq, n, ncent, nprobe, d, k, lg, pd, pr);
+  KnnIvfPlan p;
+  EULER_HIP_CHECK(knn_ivf_plan(Q, XS, 8, nq, n, ncent, nprobe, d, k, p));
+  const int lg = knn_lane_group_log2(d, p.vec ? 8 : 1);
+  hipLaunchKernelGGL(p.vec ? knn_ivf_scan_bf16_kernel<true> : knn_ivf_scan_bf16_kernel<false>, dim3(p.grid),
+                     dim3(kKnnThreads), p.lds, s, Q, XS, xn, list_ptr, row_of, probe, nq, n, ncent, nprobe, d, k, lg, pd,
+                     pr);
   return hipGetLastError();
 }
 

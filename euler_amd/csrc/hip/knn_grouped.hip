@@ -47,15 +47,12 @@ namespace euler_hip {
 
 namespace {
 
-typedef __bf16 kg_bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kGrTQ = 64;             // queries per work item
 constexpr int kGrTR = 128;            // rows of the list per tile
 constexpr int kGrHR = 64;             // rows per score half tile
 constexpr int kGrCB = 128;            // bytes of a row per LDS chunk
 constexpr int kGrLd = kGrCB + 16;     // staging row stride (bytes)
 constexpr int kGrScLd = kGrHR + 1;    // score row stride (floats)
-constexpr int kGrQW = kGrTQ / 4;      // queries owned per wave in the selection
 constexpr int kGrBuildThreads = 1024;
 constexpr size_t kGrLdsMax = 160 * 1024;
 
@@ -158,8 +155,7 @@ __device__ __forceinline__ uint4_t kg_load16(const unsigned char* __restrict__ r
 template <bool BF>
 __device__ __forceinline__ float16_t kg_mma(uint4_t x, uint4_t q, float16_t c) {
   if constexpr (BF) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(kg_bf16x8, x), __builtin_bit_cast(kg_bf16x8, q),
-                                                   c, 0, 0, 0);
+    return knn_mfma_bf16(x, q, c);
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e)
@@ -183,14 +179,9 @@ __global__ __launch_bounds__(kKnnThreads, 3) void knn_grouped_scan_kernel(
   unsigned char* Qs = Xs + kGrTR * kGrLd;                   // [TQ][qld]; a chunk [TQ][kGrLd] unless QRES
   const int qs = QRES ? qld : kGrLd;
   float* xns = reinterpret_cast<float*>(Qs + kGrTQ * qs);   // [128], +inf past the list's end
-  float* st_td = xns + kGrTR;                               // [TQ] threshold score
-  int* st_to = reinterpret_cast<int*>(st_td + kGrTQ);       // [TQ] threshold offset
-  int* st_c = st_to + kGrTQ;                                // [TQ] entries held
-  int* qflag = st_c + kGrTQ;                                // [2][TQ] half tile has a candidate
-  int* tq_pair = qflag + 2 * kGrTQ;                         // [TQ] pair of the tile's query, -1 past its end
+  const KnnSel<kGrTQ, 2, 2> st(xns + kGrTR, k);             // a flag per query and score half tile
+  int* tq_pair = st.extra;                                  // [TQ] pair of the tile's query, -1 past its end
   int* tq_q = tq_pair + kGrTQ;                              // [TQ] its query
-  float* ld = reinterpret_cast<float*>(tq_q + kGrTQ);       // [TQ][k]
-  int* lo = reinterpret_cast<int*>(ld + static_cast<size_t>(kGrTQ) * k);  // [TQ][k]
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
@@ -203,18 +194,12 @@ __global__ __launch_bounds__(kKnnThreads, 3) void knn_grouped_scan_kernel(
     const int p_begin = it2.y;
     int np = qptr[it2.x + 1] - p_begin;
     if (np > kGrTQ) np = kGrTQ;
-    int64_t b = list_ptr[it2.x], e = list_ptr[it2.x + 1];
-    if (b < 0) b = 0;
-    if (e > n) e = n;
-    if (e - b > INT_MAX - kGrTR) e = b + (INT_MAX - kGrTR);  // offsets inside a list are 32-bit
+    int64_t b, e;
+    knn_list_range(list_ptr, it2.x, n, kGrTR, b, e);
 
     __syncthreads();  // the previous item's lists and state are written out
+    st.reset();
     for (int i = tid; i < kGrTQ; i += kKnnThreads) {
-      st_td[i] = inf;
-      st_to[i] = INT_MAX;
-      st_c[i] = 0;
-      qflag[i] = 0;
-      qflag[kGrTQ + i] = 0;
       const int p = i < np ? pairs[p_begin + i] : -1;
       tq_pair[i] = p;
       tq_q[i] = p >= 0 ? p / nprobe : 0;
@@ -289,85 +274,22 @@ __global__ __launch_bounds__(kKnnThreads, 3) void knn_grouped_scan_kernel(
       // selection, 64 rows at a time: wave w's rows belong to half w >> 1
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
-        int* flag = qflag + hf * kGrTQ;
         const bool mine = (w >> 1) == hf;
-        // a lane's scores of one accumulator are 16 rows against one query: flag the query if the
-        // least of them is at or under its threshold.  At hf = 1 no barrier separates this read of
-        // st_td from the owners' hf = 0 insertions, on purpose: a threshold only falls, so a stale
-        // one only flags a query that knn_wave_select then turns away; the test must stay `<=`
-        // against a value that is never below the current threshold.
-        if (mine) {
-          float xv[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) xv[r] = xns[w * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
-#pragma unroll
-          for (int a = 0; a < 2; ++a) {
-            const int ql = a * 32 + l31;
-            float m = inf;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) m = fminf(m, fmaf(-2.f, acc[a][r], xv[r]));
-            if (m <= st_td[ql]) flag[ql] = 1;
-          }
-        }
+        // a lane's scores of one accumulator are 16 rows against one query (KnnSel::tile_flag)
+        if (mine) st.tile_flag(hf, acc[0], acc[1], xns + w * 32, l31);
         __syncthreads();  // flags are set; at hf = 0 the tile's last fragment reads are done too
-        if (mine) {
-#pragma unroll
-          for (int a = 0; a < 2; ++a) {
-            const int ql = a * 32 + l31;
-            if (flag[ql] == 0) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-              sc[ql * kGrScLd + (w & 1) * 32 + i] = fmaf(-2.f, acc[a][r], xns[w * 32 + i]);
-            }
-          }
-        }
+        if (mine) st.tile_spill(hf, acc[0], acc[1], xns + w * 32, l31, sc + (w & 1) * 32, kGrScLd);
         __syncthreads();
-
-        // wave w owns queries [w * QW, (w + 1) * QW)
-        const int myq = w * kGrQW + lane;
-        const bool flagged = lane < kGrQW && flag[myq] != 0;
-        if (flagged) flag[myq] = 0;
-        uint64_t qm = __ballot(flagged);
         const int64_t h0 = x0 + hf * kGrHR;
-        const int toff = static_cast<int>(h0 - b);
-        while (qm) {
-          const int qq = __ffsll(static_cast<unsigned long long>(qm)) - 1;
-          qm &= qm - 1;
-          const int ql = w * kGrQW + qq;
-          if (ql >= np) break;
-          int c = st_c[ql];
-          float td = st_td[ql];
-          int to = st_to[ql];
-          const float s = sc[ql * kGrScLd + lane];
-          knn_wave_select(s, toff + lane, h0 + lane < e, ld + static_cast<size_t>(ql) * k,
-                          lo + static_cast<size_t>(ql) * k, k, c, td, to);
-          if (lane == 0) {
-            st_c[ql] = c;
-            st_td[ql] = td;
-            st_to[ql] = to;
-          }
-        }
+        st.select(hf, sc, kGrScLd, 0, np, static_cast<int>(h0 - b), 0, knn_count(e - h0, kGrHR));
       }
     }
 
-    // write the partial list of every pair of the tile: each wave its own queries
+    // write the partial list of every pair of the tile
     __syncthreads();
-    for (int qq = 0; qq < kGrQW; ++qq) {
-      const int ql = w * kGrQW + qq;
-      if (ql >= np) break;
-      const int c = st_c[ql];
-      const int64_t base = static_cast<int64_t>(tq_pair[ql]) * k;
-      for (int j = lane; j < k; j += 64) {
-        const bool has = j < c;
-        pd[base + j] = has ? ld[static_cast<size_t>(ql) * k + j] : inf;
-        pr[base + j] = has ? row_of[b + lo[static_cast<size_t>(ql) * k + j]] : int64_t{-1};
-      }
-    }
+    st.write_back(0, np, pd, pr, [&](int ql) { return static_cast<int64_t>(tq_pair[ql]) * k; }, KnnRowOf{row_of, b});
   }
 }
-
-bool kg_aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 
@@ -409,11 +331,10 @@ hipError_t eh_knn_grouped_scan(const void* Q, const void* XS, int bf16, const fl
       d > (INT_MAX - kGrCB) / es || k < 1 || k > kKnnMaxK || nq > INT_MAX / nprobe || max_items < 1)
     return hipErrorInvalidValue;
   const int rowbytes = d * es;
-  const bool vec = rowbytes % 16 == 0 && kg_aligned16(Q) && kg_aligned16(XS);
+  const bool vec = rowbytes % 16 == 0 && knn_aligned16(Q) && knn_aligned16(XS);
   const int64_t qld = ceil_div(rowbytes, kGrCB) * kGrCB + 16;
-  // row staging, norms, the seven per-query words, the lists
-  const size_t base = static_cast<size_t>(kGrTR) * kGrLd + sizeof(float) * (kGrTR + 7 * kGrTQ) +
-                      sizeof(float) * 2 * static_cast<size_t>(kGrTQ) * k;
+  // row staging, norms, the selection state with the two words (pair, query) of this kernel
+  const size_t base = static_cast<size_t>(kGrTR) * kGrLd + sizeof(float) * kGrTR + knn_sel_bytes(kGrTQ, 2, 2, k);
   const bool qres = base + static_cast<size_t>(kGrTQ) * qld <= kGrLdsMax;
   const size_t lds = base + static_cast<size_t>(kGrTQ) * (qres ? qld : kGrLd);
   const int grid = knn_grid(max_items, 4096);

@@ -45,7 +45,7 @@ def _dev(t):
     return t.float().contiguous().cuda()
 
 
-@pytest.mark.parametrize("d", [4, 20, 128, 200])
+@pytest.mark.parametrize("d", [4, 7, 20, 67, 128, 200])  # 7 and 67 are no multiple of 4: scalar loads
 @pytest.mark.parametrize("nq", [1, 7, 130])
 @pytest.mark.parametrize("k", [1, 10, 128])
 def test_flat_scan_shapes(d, nq, k):
@@ -117,7 +117,7 @@ def _ivf_oracle(x, q, assign, probe, k):
     return D, I
 
 
-@pytest.mark.parametrize("d", [20, 128])
+@pytest.mark.parametrize("d", [7, 20, 128])
 def test_ivf_scan(d):
     x, q, assign, probe = _ivf_case(d)
     list_ptr, row_of = knn_ops.build_lists(assign, 7)
